@@ -10,11 +10,19 @@ on flattened bf16 params + fp32 master.
 
 Usage:
   python bench.py [--gpus N] [--steps K] [--warmup W] [--batch-size B]
+                  [--dump-outputs DIR] [--full]
   # N>1 is launched by the driver as:
   #   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
   #       --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Rank 0 prints ONE JSON line with the whole-job aggregate samples/sec.
+
+A plain run does only what the headline figure needs: set up, warm up, time
+the K steps, print the line. ``--full`` adds the secondary measurements (the
+in-run eager A/B that fills ``eager_value``/``vs_eager``). ``--dump-outputs
+DIR`` writes what the last timed step produced as ``DIR/<name>.npy`` so two
+builds can be compared output for output (inputs are seeded: same arguments,
+same batches).
 """
 
 import argparse
@@ -41,9 +49,17 @@ def parse_bench_args():
     p.add_argument("--cpu", action="store_true", help="debug: run on CPU fp32")
     p.add_argument("--eager", action="store_true",
                    help="self-baseline: disable the HIP kernels (eager ops)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements: the short "
+                        "eager A/B pass that populates eager_value/vs_eager "
+                        "in the JSON line (runs at N=1 only)")
     p.add_argument("--no-eager-ab", action="store_true",
-                   help="skip the short eager A/B pass that populates "
-                        "vs_eager in the JSON line (runs at N=1 only)")
+                   help="with --full: skip the eager A/B pass")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed "
+                        "step produced (its logging output and a fixed "
+                        "seeded sample of the updated parameters) as "
+                        "DIR/<name>.npy")
     p.add_argument("--live-loader", action="store_true",
                    help="time the REAL data pipeline (EpochBatchIterator + "
                         "BufferedIterator + CudaPrefetcher) instead of "
@@ -106,10 +122,44 @@ def disable_kernels():
     ops._kernels = None
 
 
+DUMP_SAMPLE_PER_PARAM = 16384  # ~200 tensors -> ~13 MB of float32
+DUMP_SEED = 1234
+
+
+@torch.no_grad()
+def dump_outputs(out_dir, trainer, logs):
+    """Write what a caller of the timed train_step holds after the last timed
+    step: each number of its returned logging output (``log_<key>.npy``,
+    float64) and the updated model parameters (``params.npy``, float32).
+    Tensors larger than DUMP_SAMPLE_PER_PARAM contribute a fixed seeded
+    sample of their elements, so the whole dump stays far below 64 MB."""
+    os.makedirs(out_dir, exist_ok=True)
+    for key, val in sorted((logs or {}).items()):
+        if torch.is_tensor(val):
+            val = val.detach().double().cpu().numpy()
+        try:
+            arr = np.atleast_1d(np.asarray(val, dtype=np.float64))
+        except (TypeError, ValueError):
+            continue
+        np.save(os.path.join(out_dir, f"log_{key}.npy"), arr)
+
+    rng = np.random.default_rng(DUMP_SEED)
+    chunks = []
+    for _, p in trainer.get_model().named_parameters():
+        flat = p.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE_PER_PARAM:
+            idx = np.sort(rng.choice(flat.numel(), DUMP_SAMPLE_PER_PARAM,
+                                     replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        chunks.append(flat.float().cpu().numpy())
+    np.save(os.path.join(out_dir, "params.npy"), np.concatenate(chunks))
+
+
 def run_training_loop(b, world_size, rank, local_rank, use_cuda, steps,
-                      warmup, live_loader=False):
+                      warmup, live_loader=False, dump_dir=None):
     """Build task/model/trainer fresh and time *steps* updates; returns
-    (samples_per_sec, elapsed_seconds)."""
+    (samples_per_sec, elapsed_seconds). With *dump_dir*, rank 0 then writes
+    the last timed step's outputs there."""
     from unicore_amd import tasks
     from unicore_amd.trainer import Trainer
 
@@ -130,7 +180,7 @@ def run_training_loop(b, world_size, rank, local_rank, use_cuda, steps,
         # the REAL pipeline in the timed region: DataLoader workers ->
         # BufferedIterator thread -> CudaPrefetcher copy stream
         def one_step(i):
-            trainer.train_step([next(itr)])
+            return trainer.train_step([next(itr)])
     else:
         # pre-collated batch cycle; H2D still happens inside train_step
         # via _prepare_sample (non_blocking pinned copies)
@@ -142,7 +192,7 @@ def run_training_loop(b, world_size, rank, local_rank, use_cuda, steps,
         assert cpu_batches, "no batches produced"
 
         def one_step(i):
-            trainer.train_step([cpu_batches[i % len(cpu_batches)]])
+            return trainer.train_step([cpu_batches[i % len(cpu_batches)]])
 
     def barrier_sync():
         if world_size > 1:
@@ -154,10 +204,14 @@ def run_training_loop(b, world_size, rank, local_rank, use_cuda, steps,
         one_step(i)
     barrier_sync()
     t0 = time.perf_counter()
+    logs = None
     for i in range(steps):
-        one_step(warmup + i)
+        logs = one_step(warmup + i)
     barrier_sync()
     elapsed = time.perf_counter() - t0
+
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, trainer, logs)
 
     if world_size > 1:
         t = torch.tensor([elapsed], device="cuda" if use_cuda else "cpu")
@@ -206,15 +260,15 @@ def main():
 
     samples_per_sec, elapsed = run_training_loop(
         b, world_size, rank, local_rank, use_cuda, b.steps, b.warmup,
-        live_loader=b.live_loader,
+        live_loader=b.live_loader, dump_dir=b.dump_outputs,
     )
 
-    # short in-run eager A/B (same box, same process): quantifies the HIP
-    # kernel set against eager torch so the speedup lands in BENCH_rNN.json
+    # --full: short in-run eager A/B (same box, same process): quantifies the
+    # HIP kernel set against eager torch so the speedup lands in the JSON line
     eager_sps = None
     run_ab = (
-        use_cuda and world_size == 1 and not b.eager and not b.no_eager_ab
-        and not b.live_loader
+        b.full and use_cuda and world_size == 1 and not b.eager
+        and not b.no_eager_ab and not b.live_loader
     )
     if run_ab:
         disable_kernels()

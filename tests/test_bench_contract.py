@@ -7,6 +7,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -17,10 +19,11 @@ def _last_json_line(out):
     raise AssertionError(f"no JSON line in output:\n{out[-2000:]}")
 
 
-def test_bench_single_process_cpu():
+def test_bench_single_process_cpu(tmp_path):
     r = subprocess.run(
         [sys.executable, "bench.py", "--cpu", "--steps", "2", "--warmup", "1",
-         "--batch-size", "2", "--seq-len", "64"],
+         "--batch-size", "2", "--seq-len", "64",
+         "--dump-outputs", str(tmp_path / "out")],
         cwd=REPO, capture_output=True, text=True, timeout=900,
     )
     assert r.returncode == 0, r.stderr[-2000:]
@@ -29,6 +32,20 @@ def test_bench_single_process_cpu():
     assert j["value"] > 0 and j["scaling"] == "weak"
     assert j["config"]["parallelism"] == "dp1"
     assert j["data"] == "synthetic"
+    assert j["ms_per_step"] > 0
+    # a plain run carries no secondary measurements (those need --full)
+    assert "eager_value" not in j and "vs_eager" not in j
+
+    # --dump-outputs: the last timed step's outputs as float .npy files
+    dumped = {f.name: np.load(f) for f in (tmp_path / "out").iterdir()}
+    assert {"params.npy", "log_loss.npy"} <= set(dumped)
+    total = 0
+    for name, arr in dumped.items():
+        assert name.endswith(".npy")
+        assert arr.dtype in (np.float32, np.float64), (name, arr.dtype)
+        assert np.isfinite(arr).all(), name
+        total += arr.nbytes
+    assert 0 < total <= 64 * 2**20
 
 
 def test_bench_torchrun_two_ranks_cpu():
