@@ -101,6 +101,7 @@ std::vector<at::Tensor> flash_attn_backward(
     at::Tensor lse, std::optional<at::Tensor> bias, int64_t bias_outer_div,
     bool bias_needs_grad, std::optional<at::Tensor> mask, int64_t mask_outer_div,
     double dropout_p, bool dropped, int64_t seed_in);
+at::Tensor tri_contract(at::Tensor a, at::Tensor b);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("softmax_dropout_forward", &softmax_dropout_forward,
@@ -169,4 +170,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused pair-bias kernel supports this K/H");
   m.def("cross_entropy_backward", &cross_entropy_backward,
         "cross entropy backward (softmax - onehot, no materialized fp32)");
+  m.def("tri_contract", &tri_contract,
+        "channel-last triangle contraction: (B,X,Z,C) x (B,Y,Z,C) -> (B,X,Y,C)");
 }

@@ -36,6 +36,7 @@ HIP_SOURCES = [
     "csrc/cross_entropy.hip",
     "csrc/gaussian.hip",
     "csrc/gated.hip",
+    "csrc/triangle.hip",
 ]
 
 setup(

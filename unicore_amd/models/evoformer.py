@@ -30,6 +30,7 @@ from unicore_amd.modules import (
     gated_mul,
     gelu_dropout,
     softmax_dropout,
+    triangle_multiply,
 )
 from unicore_amd.modules.dropout_add_ln import dropout_add_ln_pre
 from unicore_amd.modules.embedding import Embedding
@@ -204,10 +205,7 @@ class TriangleMultiplication(nn.Module):
         else:
             a = self.a_proj(p) * torch.sigmoid(self.a_gate(p))  # (B, I, J, c)
             b = self.b_proj(p) * torch.sigmoid(self.b_gate(p))
-        if self.outgoing:
-            o = torch.einsum("bikc,bjkc->bijc", a, b)
-        else:
-            o = torch.einsum("bkic,bkjc->bijc", a, b)
+        o = triangle_multiply(a, b, self.outgoing)
         if _fold_ok(self.out.bias, self.gate.bias):
             return gated_mul(F.linear(self.out_norm(o), self.out.weight),
                              F.linear(p, self.gate.weight),

@@ -7,6 +7,7 @@ from .gelu_dropout import gelu_dropout
 from .dropout_add import dropout_add
 from .gaussian import gaussian_basis
 from .gated_mul import gated_mul
+from .triangle import triangle_multiply
 from .embedding import Embedding
 from .multihead_attention import SelfMultiheadAttention, CrossMultiheadAttention
 from .transformer_encoder_layer import TransformerEncoderLayer

@@ -300,3 +300,19 @@ def msa_arrange(x, B, S, L, heads, col, inverse=False):
     return _kernels.msa_arrange(
         x, int(B), int(S), int(L), int(heads), bool(col), bool(inverse)
     )
+
+
+def tri_contract(a, b):
+    """O[b,x,y,c] = sum_z a[b,x,z,c] * b[b,y,z,c] on channel-last bf16
+    tensors; the two spatial strides of a and b are free (transpose(1, 2)
+    views are read in place), the result is contiguous (B, X, Y, C)."""
+    require_kernels()
+    return _kernels.tri_contract(a, b)
+
+
+def tri_contract_supported(C, dtype) -> bool:
+    # mirrors the host check in csrc/triangle.hip (16-channel block chunk);
+    # pure Python so a missing extension still fails loudly in tri_contract
+    import torch
+
+    return dtype == torch.bfloat16 and int(C) > 0 and int(C) % 16 == 0
