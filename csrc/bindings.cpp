@@ -102,6 +102,9 @@ std::vector<at::Tensor> flash_attn_backward(
     bool bias_needs_grad, std::optional<at::Tensor> mask, int64_t mask_outer_div,
     double dropout_p, bool dropped, int64_t seed_in);
 at::Tensor tri_contract(at::Tensor a, at::Tensor b);
+at::Tensor opm_forward(at::Tensor a, at::Tensor b, double scale);
+at::Tensor opm_backward_a(at::Tensor d_o, at::Tensor b, double scale);
+at::Tensor opm_backward_b(at::Tensor d_o, at::Tensor a, double scale);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("softmax_dropout_forward", &softmax_dropout_forward,
@@ -172,4 +175,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "cross entropy backward (softmax - onehot, no materialized fp32)");
   m.def("tri_contract", &tri_contract,
         "channel-last triangle contraction: (B,X,Z,C) x (B,Y,Z,C) -> (B,X,Y,C)");
+  m.def("opm_forward", &opm_forward,
+        "outer product mean: (B,S,I,32) x (B,S,J,32) -> (B,I,J,32,32)");
+  m.def("opm_backward_a", &opm_backward_a,
+        "outer product mean, gradient of a: (B,I,J,32,32) x (B,S,J,32) -> (B,S,I,32)");
+  m.def("opm_backward_b", &opm_backward_b,
+        "outer product mean, gradient of b: (B,I,J,32,32) x (B,S,I,32) -> (B,S,J,32)");
 }

@@ -37,6 +37,7 @@ HIP_SOURCES = [
     "csrc/gaussian.hip",
     "csrc/gated.hip",
     "csrc/triangle.hip",
+    "csrc/outer_product.hip",
 ]
 
 setup(

@@ -31,6 +31,7 @@ from unicore_amd.modules import (
     gelu_dropout,
     softmax_dropout,
     triangle_multiply,
+    outer_product_mean,
 )
 from unicore_amd.modules.dropout_add_ln import dropout_add_ln_pre
 from unicore_amd.modules.embedding import Embedding
@@ -172,8 +173,7 @@ class OuterProductMean(nn.Module):
         x = self.norm(msa) if x_normed is None else x_normed
         a = self.a(x)  # (B, S, L, c)
         b = self.b(x)
-        o = torch.einsum("bsic,bsjd->bijcd", a.float(), b.float()) / msa.shape[1]
-        o = o.reshape(*o.shape[:3], self.c * self.c).to(msa.dtype)
+        o = outer_product_mean(a, b)  # (B, L, L, c*c), mean over S
         if skip_out_bias:
             return F.linear(o, self.out.weight)
         return self.out(o)

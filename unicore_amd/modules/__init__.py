@@ -8,6 +8,7 @@ from .dropout_add import dropout_add
 from .gaussian import gaussian_basis
 from .gated_mul import gated_mul
 from .triangle import triangle_multiply
+from .outer_product import outer_product_mean
 from .embedding import Embedding
 from .multihead_attention import SelfMultiheadAttention, CrossMultiheadAttention
 from .transformer_encoder_layer import TransformerEncoderLayer

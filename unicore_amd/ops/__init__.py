@@ -316,3 +316,30 @@ def tri_contract_supported(C, dtype) -> bool:
     import torch
 
     return dtype == torch.bfloat16 and int(C) > 0 and int(C) % 16 == 0
+
+
+def opm_fwd(a, b, scale):
+    """o[b,i,j,c,d] = scale * sum_s a[b,s,i,c] * b[b,s,j,d]; a (B,S,I,32) and
+    b (B,S,J,32) contiguous bf16, result contiguous (B,I,J,32,32)."""
+    require_kernels()
+    return _kernels.opm_forward(a, b, float(scale))
+
+
+def opm_bwd_a(d_o, b, scale):
+    """da[b,s,i,c] = scale * sum_{j,d} d_o[b,i,j,c,d] * b[b,s,j,d]."""
+    require_kernels()
+    return _kernels.opm_backward_a(d_o, b, float(scale))
+
+
+def opm_bwd_b(d_o, a, scale):
+    """db[b,s,j,d] = scale * sum_{i,c} d_o[b,i,j,c,d] * a[b,s,i,c]."""
+    require_kernels()
+    return _kernels.opm_backward_b(d_o, a, float(scale))
+
+
+def opm_supported(c, d, dtype) -> bool:
+    # mirrors the host check in csrc/outer_product.hip (width 32 only);
+    # pure Python so a missing extension still fails loudly in opm_fwd
+    import torch
+
+    return dtype == torch.bfloat16 and int(c) == 32 and int(d) == 32
