@@ -105,6 +105,12 @@ at::Tensor tri_contract(at::Tensor a, at::Tensor b);
 at::Tensor opm_forward(at::Tensor a, at::Tensor b, double scale);
 at::Tensor opm_backward_a(at::Tensor d_o, at::Tensor b, double scale);
 at::Tensor opm_backward_b(at::Tensor d_o, at::Tensor a, double scale);
+at::Tensor pair_arrange(at::Tensor x, int64_t heads, bool transpose);
+at::Tensor pair_merge(at::Tensor o, int64_t B, int64_t I, int64_t J,
+                      int64_t heads, bool transpose,
+                      std::optional<at::Tensor> out);
+at::Tensor pair_bias_arrange(at::Tensor lin, bool transpose);
+at::Tensor pair_bias_arrange_bwd(at::Tensor d_bias, bool transpose);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("softmax_dropout_forward", &softmax_dropout_forward,
@@ -181,4 +187,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "outer product mean, gradient of a: (B,I,J,32,32) x (B,S,J,32) -> (B,S,I,32)");
   m.def("opm_backward_b", &opm_backward_b,
         "outer product mean, gradient of b: (B,I,J,32,32) x (B,S,I,32) -> (B,S,J,32)");
+  m.def("pair_arrange", &pair_arrange,
+        "triangle attention: (B,I,J,H*D) view -> (B,H,R,T,D), optionally transposed");
+  m.def("pair_merge", &pair_merge,
+        "triangle attention: (B*H*R,T,D) -> (B,I,J,H*D), inverse of pair_arrange");
+  m.def("pair_bias_arrange", &pair_bias_arrange,
+        "triangle attention bias: (B,L,L,H) -> (B,H,L,L), optionally transposed");
+  m.def("pair_bias_arrange_bwd", &pair_bias_arrange_bwd,
+        "triangle attention bias gradient: (B,H,L,L) -> (B,L,L,H)");
 }

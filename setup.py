@@ -38,6 +38,7 @@ HIP_SOURCES = [
     "csrc/gated.hip",
     "csrc/triangle.hip",
     "csrc/outer_product.hip",
+    "csrc/tri_attn.hip",
 ]
 
 setup(

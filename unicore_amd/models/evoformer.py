@@ -6,7 +6,10 @@ pair bias (the fused softmax_dropout 5-D broadcast path: scores arranged
 (src_nb, outer_div) addressing with no materialized broadcast), MSA column
 attention, MSA transition, outer-product-mean pair update, triangle
 multiplication (outgoing + incoming) and pair transition — all through the
-framework's fused LayerNorm.  Intended to run bf16 + stochastic rounding
+framework's fused LayerNorm.  ``--triangle-attention`` adds the other two
+pair-stack modules, triangle self-attention around the starting and the
+ending node (modules/triangle_attention.py), between the incoming triangle
+multiplication and the pair transition.  Intended to run bf16 + stochastic rounding
 with grad accumulation (exercising the rounding and multi-tensor kernels).
 """
 
@@ -35,6 +38,7 @@ from unicore_amd.modules import (
 )
 from unicore_amd.modules.dropout_add_ln import dropout_add_ln_pre
 from unicore_amd.modules.embedding import Embedding
+from unicore_amd.modules.triangle_attention import TriangleAttention
 
 
 def _fold_ok(*biases):
@@ -215,7 +219,8 @@ class TriangleMultiplication(nn.Module):
 
 
 class EvoformerBlock(nn.Module):
-    def __init__(self, d_msa, d_pair, heads, dropout):
+    def __init__(self, d_msa, d_pair, heads, dropout,
+                 triangle_attention=False, tri_attn_heads=4):
         super().__init__()
         self.row_attn = MSARowAttentionWithPairBias(d_msa, d_pair, heads, dropout)
         self.col_attn = MSAColumnAttention(d_msa, heads, dropout)
@@ -224,6 +229,14 @@ class EvoformerBlock(nn.Module):
         self.tri_out = TriangleMultiplication(d_pair, outgoing=True)
         self.tri_in = TriangleMultiplication(d_pair, outgoing=False)
         self.pair_transition = Transition(d_pair)
+        # constructed last and only on request: without the flag the
+        # parameter names and the initialisation order are unchanged
+        self.triangle_attention = triangle_attention
+        if triangle_attention:
+            self.tri_att_start = TriangleAttention(d_pair, tri_attn_heads,
+                                                   dropout, starting=True)
+            self.tri_att_end = TriangleAttention(d_pair, tri_attn_heads,
+                                                 dropout, starting=False)
 
     def forward(self, msa, pair):
         fold = msa.is_cuda and _fold_ok(
@@ -232,6 +245,9 @@ class EvoformerBlock(nn.Module):
             self.opm.out.bias,
             self.pair_transition.fc1.bias, self.pair_transition.fc2.bias,
         )
+        if fold and self.triangle_attention:
+            fold = _fold_ok(self.tri_att_start.out.bias,
+                            self.tri_att_end.out.bias)
         if fold:
             # pre-LN residual chain: each join is ONE fused kernel emitting
             # both the summed stream and the next sub-module's normed input
@@ -254,8 +270,20 @@ class EvoformerBlock(nn.Module):
             y = self.tri_out(pair, p_normed=pn)
             pair, pn = dropout_add_ln_pre(y, pair, self.tri_in.norm, 0.0, t)
             y = self.tri_in(pair, p_normed=pn)
-            pair, pn = dropout_add_ln_pre(y, pair, self.pair_transition.norm,
-                                          0.0, t)
+            if self.triangle_attention:
+                pair, pn = dropout_add_ln_pre(y, pair, self.tri_att_start.norm,
+                                              0.0, t)
+                y = self.tri_att_start(pair, skip_out_bias=True, p_normed=pn)
+                pair, pn = dropout_add_ln_pre(
+                    y, pair, self.tri_att_end.norm, 0.0, t,
+                    bias=self.tri_att_start.out.bias)
+                y = self.tri_att_end(pair, skip_out_bias=True, p_normed=pn)
+                pair, pn = dropout_add_ln_pre(
+                    y, pair, self.pair_transition.norm, 0.0, t,
+                    bias=self.tri_att_end.out.bias)
+            else:
+                pair, pn = dropout_add_ln_pre(y, pair,
+                                              self.pair_transition.norm, 0.0, t)
             y = self.pair_transition.tail(pn)
             pair = dropout_add(y, pair, 0.0, t,
                                bias=self.pair_transition.fc2.bias)
@@ -266,6 +294,9 @@ class EvoformerBlock(nn.Module):
         pair = pair + self.opm(msa)
         pair = pair + self.tri_out(pair)
         pair = pair + self.tri_in(pair)
+        if self.triangle_attention:
+            pair = pair + self.tri_att_start(pair)
+            pair = pair + self.tri_att_end(pair)
         pair = self.pair_transition(pair, residual=pair)
         return msa, pair
 
@@ -287,6 +318,13 @@ class EvoformerModel(BaseUnicoreModel):
         parser.add_argument("--activation-checkpoint", action="store_true",
                             help="recompute each Evoformer block in "
                                  "backward (utils.checkpoint_sequential)")
+        parser.add_argument("--triangle-attention", action="store_true",
+                            help="add triangle self-attention (starting and "
+                                 "ending node) to every block's pair stack, "
+                                 "between the incoming triangle "
+                                 "multiplication and the pair transition")
+        parser.add_argument("--tri-attn-heads", type=int, metavar="N",
+                            help="heads of the triangle attention modules")
         parser.add_argument("--hip-graph-blocks", action="store_true",
                             help="capture each Evoformer block as a hipGraph "
                                  "(fwd+bwd) and replay it — removes the "
@@ -309,7 +347,9 @@ class EvoformerModel(BaseUnicoreModel):
         self.blocks = nn.ModuleList(
             [
                 EvoformerBlock(args.msa_dim, args.pair_dim, args.evo_heads,
-                               args.dropout)
+                               args.dropout,
+                               triangle_attention=args.triangle_attention,
+                               tri_attn_heads=args.tri_attn_heads)
                 for _ in range(args.evo_layers)
             ]
         )
@@ -403,3 +443,5 @@ def evoformer_base_architecture(args):
     args.recycle_iters = getattr(args, "recycle_iters", None) or 0
     args.activation_checkpoint = getattr(args, "activation_checkpoint", False)
     args.hip_graph_blocks = getattr(args, "hip_graph_blocks", False)
+    args.triangle_attention = getattr(args, "triangle_attention", False)
+    args.tri_attn_heads = getattr(args, "tri_attn_heads", None) or 4

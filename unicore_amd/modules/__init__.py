@@ -9,6 +9,13 @@ from .gaussian import gaussian_basis
 from .gated_mul import gated_mul
 from .triangle import triangle_multiply
 from .outer_product import outer_product_mean
+from .triangle_attention import (
+    TriangleAttention,
+    pair_arrange,
+    pair_arrange_qkv,
+    pair_merge,
+    pair_bias_arrange,
+)
 from .embedding import Embedding
 from .multihead_attention import SelfMultiheadAttention, CrossMultiheadAttention
 from .transformer_encoder_layer import TransformerEncoderLayer

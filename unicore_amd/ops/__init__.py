@@ -343,3 +343,41 @@ def opm_supported(c, d, dtype) -> bool:
     import torch
 
     return dtype == torch.bfloat16 and int(c) == 32 and int(d) == 32
+
+
+def pair_arrange(x, heads, transpose=False):
+    """(B, I, J, H*D) view (contiguous channels, spatial strides free) ->
+    contiguous (B, H, R, T, D) with out[b,h,r,t,:] = x[b,i,j,h*D:(h+1)*D],
+    (i, j) = (t, r) if transpose else (r, t). csrc/tri_attn.hip."""
+    require_kernels()
+    return _kernels.pair_arrange(x, int(heads), bool(transpose))
+
+
+def pair_merge(o, B, I, J, heads, transpose=False, out=None):
+    """Inverse of pair_arrange: contiguous (B*H*R, T, D) -> (B, I, J, H*D),
+    a fresh contiguous tensor, or ``out`` if given: a (B, I, J, H*D) view
+    under the layout rules of pair_arrange's input (one third of a fused
+    qkv gradient buffer, say)."""
+    require_kernels()
+    return _kernels.pair_merge(
+        o, int(B), int(I), int(J), int(heads), bool(transpose), out
+    )
+
+
+def pair_bias_arrange(lin, transpose=False):
+    """Contiguous (B, L, L, H) -> (B, H, L, L): out[b,h,x,y] = lin[b,x,y,h],
+    or lin[b,y,x,h] if transpose."""
+    require_kernels()
+    return _kernels.pair_bias_arrange(lin, bool(transpose))
+
+
+def pair_bias_arrange_bwd(d_bias, transpose=False):
+    """Inverse of pair_bias_arrange: (B, H, L, L) -> (B, L, L, H)."""
+    require_kernels()
+    return _kernels.pair_bias_arrange_bwd(d_bias, bool(transpose))
+
+
+def pair_bias_arrange_supported(H, L) -> bool:
+    # mirrors the host check in csrc/tri_attn.hip; pure Python so a missing
+    # extension still fails loudly in pair_bias_arrange
+    return int(H) in (4, 8) and int(L) >= 8 and int(L) % 8 == 0
