@@ -111,6 +111,17 @@ at::Tensor pair_merge(at::Tensor o, int64_t B, int64_t I, int64_t J,
                       std::optional<at::Tensor> out);
 at::Tensor pair_bias_arrange(at::Tensor lin, bool transpose);
 at::Tensor pair_bias_arrange_bwd(at::Tensor d_bias, bool transpose);
+std::vector<at::Tensor> shared_dropout_add_forward(
+    at::Tensor x, at::Tensor res, std::optional<at::Tensor> bias, double p,
+    int64_t shared_dim);
+std::vector<at::Tensor> shared_dropout_add_ln_forward(
+    at::Tensor x, at::Tensor res, std::optional<at::Tensor> bias,
+    at::Tensor gamma, at::Tensor beta, double p, int64_t shared_dim,
+    double eps);
+std::vector<at::Tensor> shared_dropout_add_backward(at::Tensor grad,
+                                                    at::Tensor dmask, double p,
+                                                    int64_t shared_dim,
+                                                    int64_t bias_dim);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("softmax_dropout_forward", &softmax_dropout_forward,
@@ -195,4 +206,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "triangle attention bias: (B,L,L,H) -> (B,H,L,L), optionally transposed");
   m.def("pair_bias_arrange_bwd", &pair_bias_arrange_bwd,
         "triangle attention bias gradient: (B,H,L,L) -> (B,L,L,H)");
+  m.def("shared_dropout_add_forward", &shared_dropout_add_forward,
+        "dropout shared along dim 1 or 2 of (B,R,T,C) + residual add -> (out, mask)");
+  m.def("shared_dropout_add_ln_forward", &shared_dropout_add_ln_forward,
+        "shared-axis dropout + residual + LayerNorm -> (normed, summed, mask, mean, invvar)");
+  m.def("shared_dropout_add_backward", &shared_dropout_add_backward,
+        "shared-axis dropout backward through the small mask -> (dx, dbias)");
 }

@@ -220,8 +220,14 @@ class TriangleMultiplication(nn.Module):
 
 class EvoformerBlock(nn.Module):
     def __init__(self, d_msa, d_pair, heads, dropout,
-                 triangle_attention=False, tri_attn_heads=4):
+                 triangle_attention=False, tri_attn_heads=4,
+                 msa_dropout=0.0, pair_dropout=0.0):
         super().__init__()
+        # shared-axis dropout of the residual joins (AlphaFold 2 Alg. 6):
+        # row-wise (mask shared over dim 1) after row_attn, tri_out, tri_in
+        # and tri_att_start, column-wise (dim 2) after tri_att_end
+        self.msa_dropout = msa_dropout
+        self.pair_dropout = pair_dropout
         self.row_attn = MSARowAttentionWithPairBias(d_msa, d_pair, heads, dropout)
         self.col_attn = MSAColumnAttention(d_msa, heads, dropout)
         self.msa_transition = Transition(d_msa)
@@ -237,6 +243,13 @@ class EvoformerBlock(nn.Module):
                                                    dropout, starting=True)
             self.tri_att_end = TriangleAttention(d_pair, tri_attn_heads,
                                                  dropout, starting=False)
+
+    def _join(self, y, residual, p, shared_dim):
+        """Residual join of the plain chain; a plain add unless shared
+        dropout is on."""
+        if self.training and p > 0:
+            return dropout_add(y, residual, p, True, shared_dim=shared_dim)
+        return residual + y
 
     def forward(self, msa, pair):
         fold = msa.is_cuda and _fold_ok(
@@ -254,10 +267,18 @@ class EvoformerBlock(nn.Module):
             # (the 6 standalone LayerNorms + 6 residual adds per block
             # collapse into the joins; only the block's first norm remains)
             t = self.training
+            # shared_dim only where dropout is on: at 0 the joins are the
+            # unshared ones (shared_dim=None is their default)
+            md = self.msa_dropout if t else 0.0
+            pd = self.pair_dropout if t else 0.0
+            mrow = 1 if md > 0 else None
+            prow = 1 if pd > 0 else None
+            pcol = 2 if pd > 0 else None
             n = self.row_attn.norm(msa)
             y = self.row_attn(msa, pair, skip_out_bias=True, x_normed=n)
-            msa, n = dropout_add_ln_pre(y, msa, self.col_attn.norm, 0.0, t,
-                                        bias=self.row_attn.out.bias)
+            msa, n = dropout_add_ln_pre(y, msa, self.col_attn.norm, md, t,
+                                        bias=self.row_attn.out.bias,
+                                        shared_dim=mrow)
             y = self.col_attn(msa, skip_out_bias=True, x_normed=n)
             msa, n = dropout_add_ln_pre(y, msa, self.msa_transition.norm, 0.0,
                                         t, bias=self.col_attn.out.bias)
@@ -268,35 +289,39 @@ class EvoformerBlock(nn.Module):
             pair, pn = dropout_add_ln_pre(y, pair, self.tri_out.norm, 0.0, t,
                                           bias=self.opm.out.bias)
             y = self.tri_out(pair, p_normed=pn)
-            pair, pn = dropout_add_ln_pre(y, pair, self.tri_in.norm, 0.0, t)
+            pair, pn = dropout_add_ln_pre(y, pair, self.tri_in.norm, pd, t,
+                                          shared_dim=prow)
             y = self.tri_in(pair, p_normed=pn)
             if self.triangle_attention:
                 pair, pn = dropout_add_ln_pre(y, pair, self.tri_att_start.norm,
-                                              0.0, t)
+                                              pd, t, shared_dim=prow)
                 y = self.tri_att_start(pair, skip_out_bias=True, p_normed=pn)
                 pair, pn = dropout_add_ln_pre(
-                    y, pair, self.tri_att_end.norm, 0.0, t,
-                    bias=self.tri_att_start.out.bias)
+                    y, pair, self.tri_att_end.norm, pd, t,
+                    bias=self.tri_att_start.out.bias, shared_dim=prow)
                 y = self.tri_att_end(pair, skip_out_bias=True, p_normed=pn)
                 pair, pn = dropout_add_ln_pre(
-                    y, pair, self.pair_transition.norm, 0.0, t,
-                    bias=self.tri_att_end.out.bias)
+                    y, pair, self.pair_transition.norm, pd, t,
+                    bias=self.tri_att_end.out.bias, shared_dim=pcol)
             else:
                 pair, pn = dropout_add_ln_pre(y, pair,
-                                              self.pair_transition.norm, 0.0, t)
+                                              self.pair_transition.norm, pd, t,
+                                              shared_dim=prow)
             y = self.pair_transition.tail(pn)
             pair = dropout_add(y, pair, 0.0, t,
                                bias=self.pair_transition.fc2.bias)
             return msa, pair
-        msa = msa + self.row_attn(msa, pair)
+        msa = self._join(self.row_attn(msa, pair), msa, self.msa_dropout, 1)
         msa = msa + self.col_attn(msa)
         msa = self.msa_transition(msa, residual=msa)
         pair = pair + self.opm(msa)
-        pair = pair + self.tri_out(pair)
-        pair = pair + self.tri_in(pair)
+        pair = self._join(self.tri_out(pair), pair, self.pair_dropout, 1)
+        pair = self._join(self.tri_in(pair), pair, self.pair_dropout, 1)
         if self.triangle_attention:
-            pair = pair + self.tri_att_start(pair)
-            pair = pair + self.tri_att_end(pair)
+            pair = self._join(self.tri_att_start(pair), pair,
+                              self.pair_dropout, 1)
+            pair = self._join(self.tri_att_end(pair), pair,
+                              self.pair_dropout, 2)
         pair = self.pair_transition(pair, residual=pair)
         return msa, pair
 
@@ -310,6 +335,17 @@ class EvoformerModel(BaseUnicoreModel):
         parser.add_argument("--pair-dim", type=int, metavar="N")
         parser.add_argument("--evo-heads", type=int, metavar="N")
         parser.add_argument("--dropout", type=float)
+        parser.add_argument("--msa-dropout", type=float, metavar="P",
+                            help="row-wise shared dropout (one mask per "
+                                 "residue column, shared over the MSA depth) "
+                                 "at the join after MSA row attention; "
+                                 "AlphaFold 2 trains with 0.15")
+        parser.add_argument("--pair-dropout", type=float, metavar="P",
+                            help="shared dropout at the joins after both "
+                                 "triangle multiplications and the starting "
+                                 "node attention (row-wise) and after the "
+                                 "ending node attention (column-wise); "
+                                 "AlphaFold 2 trains with 0.25")
         parser.add_argument("--max-rel-pos", type=int)
         parser.add_argument("--recycle-iters", type=int,
                             help="AlphaFold-style recycling: run the block "
@@ -349,7 +385,9 @@ class EvoformerModel(BaseUnicoreModel):
                 EvoformerBlock(args.msa_dim, args.pair_dim, args.evo_heads,
                                args.dropout,
                                triangle_attention=args.triangle_attention,
-                               tri_attn_heads=args.tri_attn_heads)
+                               tri_attn_heads=args.tri_attn_heads,
+                               msa_dropout=args.msa_dropout,
+                               pair_dropout=args.pair_dropout)
                 for _ in range(args.evo_layers)
             ]
         )
@@ -385,6 +423,12 @@ class EvoformerModel(BaseUnicoreModel):
                 "--hip-graph-blocks requires --dropout 0: the dropout "
                 "kernels key philox off a kernel argument, which graph "
                 "replay would freeze"
+            )
+            assert self.args.msa_dropout == 0 and \
+                self.args.pair_dropout == 0, (
+                "--hip-graph-blocks requires --msa-dropout 0 and "
+                "--pair-dropout 0: the shared-dropout joins key philox off "
+                "a kernel argument too"
             )
             assert not self.activation_checkpoint, (
                 "--hip-graph-blocks and --activation-checkpoint are "
@@ -439,6 +483,8 @@ def evoformer_base_architecture(args):
     args.pair_dim = getattr(args, "pair_dim", 128)
     args.evo_heads = getattr(args, "evo_heads", 8)
     args.dropout = getattr(args, "dropout", 0.1)
+    args.msa_dropout = getattr(args, "msa_dropout", None) or 0.0
+    args.pair_dropout = getattr(args, "pair_dropout", None) or 0.0
     args.max_rel_pos = getattr(args, "max_rel_pos", 32)
     args.recycle_iters = getattr(args, "recycle_iters", None) or 0
     args.activation_checkpoint = getattr(args, "activation_checkpoint", False)

@@ -41,8 +41,21 @@ class _DropoutAdd(torch.autograd.Function):
         return dx, grad, dbias, None, None
 
 
-def dropout_add(x, residual, p, is_training, bias=None):
-    """residual + dropout(x + bias, p), fused on GPU."""
+def dropout_add(x, residual, p, is_training, bias=None, shared_dim=None):
+    """residual + dropout(x + bias, p), fused on GPU.
+
+    ``shared_dim`` (1 or 2, 4-D input): one keep-mask per slice, broadcast
+    along that axis (modules/shared_dropout.py)."""
+    if shared_dim is not None:
+        from unicore_amd.modules import shared_dropout as sd
+
+        sd.check_shared_dim(x, shared_dim)
+        if is_training and p > 0:
+            if sd.fuse_ok(x, residual, bias):
+                return sd._SharedDropoutAdd.apply(x, residual, bias, p,
+                                                  shared_dim)
+            x = sd.apply_shared_mask(x, p, shared_dim, bias)
+            p, bias = 0.0, None
     if x.is_cuda and x.numel() % 8 == 0 and x.shape == residual.shape:
         from unicore_amd import ops
 

@@ -114,10 +114,36 @@ def _fuse_ok(x, residual, bias):
                         or not ops.allow_eager_on_gpu())
 
 
-def dropout_add_ln_pre(x, residual, ln, p, is_training, bias=None):
+def _shared(x, residual, bias, p, is_training, shared_dim, fn, ln):
+    """shared_dim handling common to both joins: returns the fused result,
+    or None with (x, p, bias) rewritten for the caller's p = 0 expression."""
+    from unicore_amd.modules import shared_dropout as sd
+
+    sd.check_shared_dim(x, shared_dim)
+    if not (is_training and p > 0):
+        return None, x, p, bias
+    if (_fuse_ok(x, residual, bias) and sd.fuse_ok(x, residual, bias)
+            and ln.weight.dtype == x.dtype and ln.bias.dtype == x.dtype):
+        return fn.apply(x, residual, bias, ln.weight, ln.bias, p, shared_dim,
+                        ln.eps), x, p, bias
+    return None, sd.apply_shared_mask(x, p, shared_dim, bias), 0.0, None
+
+
+def dropout_add_ln_pre(x, residual, ln, p, is_training, bias=None,
+                       shared_dim=None):
     """Pre-LN residual chain step: ``s = residual + dropout(x + bias)``;
     returns ``(s, ln(s))`` — *s* continues the residual stream, ``ln(s)``
-    feeds the next sub-module. Fused into one kernel on GPU."""
+    feeds the next sub-module. Fused into one kernel on GPU.
+
+    ``shared_dim`` (1 or 2, 4-D input): one keep-mask per slice, broadcast
+    along that axis (modules/shared_dropout.py)."""
+    if shared_dim is not None:
+        from unicore_amd.modules.shared_dropout import _SharedDropoutAddLNPre
+
+        out, x, p, bias = _shared(x, residual, bias, p, is_training,
+                                  shared_dim, _SharedDropoutAddLNPre, ln)
+        if out is not None:
+            return out
     if _fuse_ok(x, residual, bias):
         return _DropoutAddLNPre.apply(
             x, residual, bias, ln.weight, ln.bias, p, is_training, ln.eps
@@ -130,11 +156,20 @@ def dropout_add_ln_pre(x, residual, ln, p, is_training, bias=None):
     return s, ln(s)
 
 
-def dropout_add_ln(x, residual, ln, p, is_training, bias=None):
+def dropout_add_ln(x, residual, ln, p, is_training, bias=None,
+                   shared_dim=None):
     """``ln(residual + dropout(x + bias, p))`` — fused on GPU.
 
-    *ln* is the LayerNorm module whose weight/bias/eps apply.
+    *ln* is the LayerNorm module whose weight/bias/eps apply;
+    ``shared_dim`` as in ``dropout_add_ln_pre``.
     """
+    if shared_dim is not None:
+        from unicore_amd.modules.shared_dropout import _SharedDropoutAddLN
+
+        out, x, p, bias = _shared(x, residual, bias, p, is_training,
+                                  shared_dim, _SharedDropoutAddLN, ln)
+        if out is not None:
+            return out
     if _fuse_ok(x, residual, bias):
         return _DropoutAddLN.apply(
             x, residual, bias, ln.weight, ln.bias, p, is_training, ln.eps

@@ -196,6 +196,48 @@ def dropout_add_bwd(grad, dmask, p, bias_dim=0):
     return _kernels.dropout_add_backward(grad, dmask, float(p), int(bias_dim))
 
 
+def shared_dropout_add_fwd(x, res, p, shared_dim, bias=None):
+    """out = res + keep * (x + bias) / (1 - p) on contiguous (B, R, T, C);
+    keep is shared along ``shared_dim`` (1 or 2). Returns (out, mask), mask
+    the small bitfield: B*T*C/8 (shared_dim 1) or B*R*C/8 bytes. p in (0, 1)."""
+    require_kernels()
+    return _kernels.shared_dropout_add_forward(
+        x, res, bias, float(p), int(shared_dim)
+    )
+
+
+def shared_dropout_add_ln_fwd(x, res, bias, gamma, beta, p, shared_dim, eps):
+    """shared_dropout_add_fwd followed by LayerNorm from registers.
+    Returns (normed, summed, mask, mean, invvar)."""
+    require_kernels()
+    return _kernels.shared_dropout_add_ln_forward(
+        x, res, bias, gamma, beta, float(p), int(shared_dim), float(eps)
+    )
+
+
+def shared_dropout_add_bwd(grad, dmask, p, shared_dim, bias_dim=0):
+    # dx = grad * keep / (1 - p) through the small mask of the forward;
+    # bias_dim > 0: also return the fp32 column-sum bias grad
+    require_kernels()
+    return _kernels.shared_dropout_add_backward(
+        grad, dmask, float(p), int(shared_dim), int(bias_dim)
+    )
+
+
+def shared_dropout_supported(shape, dtype) -> bool:
+    # mirrors the host checks in csrc/shared_dropout.hip (the LN entry also
+    # needs C <= 2048); pure Python so a missing extension still fails
+    # loudly in the wrappers above
+    import torch
+
+    return (
+        dtype in (torch.float32, torch.float16, torch.bfloat16)
+        and len(shape) == 4
+        and int(shape[3]) > 0
+        and int(shape[3]) % 8 == 0
+    )
+
+
 def colsum_supported(C) -> bool:
     import math
 
