@@ -105,6 +105,15 @@ at::Tensor tri_contract(at::Tensor a, at::Tensor b);
 at::Tensor opm_forward(at::Tensor a, at::Tensor b, double scale);
 at::Tensor opm_backward_a(at::Tensor d_o, at::Tensor b, double scale);
 at::Tensor opm_backward_b(at::Tensor d_o, at::Tensor a, double scale);
+at::Tensor opm_forward_w(at::Tensor a, at::Tensor b, at::Tensor w);
+at::Tensor opm_backward_a_w(at::Tensor d_o, at::Tensor b, at::Tensor w);
+at::Tensor opm_backward_b_w(at::Tensor d_o, at::Tensor a, at::Tensor w);
+at::Tensor gated_mul_masked_forward(at::Tensor x, at::Tensor g,
+                                    std::optional<at::Tensor> bx,
+                                    std::optional<at::Tensor> bg, at::Tensor m);
+std::vector<at::Tensor> gated_mul_masked_backward(
+    at::Tensor grad, at::Tensor x, at::Tensor g, std::optional<at::Tensor> bx,
+    std::optional<at::Tensor> bg, at::Tensor m);
 at::Tensor pair_arrange(at::Tensor x, int64_t heads, bool transpose);
 at::Tensor pair_merge(at::Tensor o, int64_t B, int64_t I, int64_t J,
                       int64_t heads, bool transpose,
@@ -198,6 +207,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "outer product mean, gradient of a: (B,I,J,32,32) x (B,S,J,32) -> (B,S,I,32)");
   m.def("opm_backward_b", &opm_backward_b,
         "outer product mean, gradient of b: (B,I,J,32,32) x (B,S,I,32) -> (B,S,J,32)");
+  m.def("opm_forward_w", &opm_forward_w,
+        "opm_forward with an fp32 (B,I,J) weight in place of the scale");
+  m.def("opm_backward_a_w", &opm_backward_a_w,
+        "opm_backward_a with an fp32 (B,I,J) weight in place of the scale");
+  m.def("opm_backward_b_w", &opm_backward_b_w,
+        "opm_backward_b with an fp32 (B,I,J) weight in place of the scale");
+  m.def("gated_mul_masked_forward", &gated_mul_masked_forward,
+        "fused (x+bx)*sigmoid(g+bg)*m[row]");
+  m.def("gated_mul_masked_backward", &gated_mul_masked_backward,
+        "row-masked gated-mul backward -> (dx, dg[, bias colsums])");
   m.def("pair_arrange", &pair_arrange,
         "triangle attention: (B,I,J,H*D) view -> (B,H,R,T,D), optionally transposed");
   m.def("pair_merge", &pair_merge,

@@ -52,6 +52,15 @@
 // predicated at the store.  Every output element is accumulated inside one
 // wave in a fixed order: no atomics, no split-K, bitwise reproducible.
 // Every offset product is int64_t.
+//
+// Weighted entries (opm_forward_w / opm_backward_a_w / opm_backward_b_w): a
+// contiguous fp32 w[b,i,j] takes the place of scale, for padded batches where
+// the mean's normaliser differs per pair.  They are the WT = true
+// instantiations of the same kernels; WT = false is the code as it was.
+// Forward multiplies by w in the epilogue (fp32, one rounding).  In backward
+// w varies along K, so each d_o tile is multiplied on its way into LDS and
+// rounded to bf16 once more: a relative 2^-8 per product on top of the
+// unweighted error.  Same fixed accumulation order, same reproducibility.
 #include "common.h"
 
 #include <torch/extension.h>
@@ -129,13 +138,27 @@ __device__ __forceinline__ uint2 opm_pack4(const f32x4& v, float scale) {
   return o;
 }
 
+// 8 bf16 -> fp32, times w, rounded back to bf16 (weighted backward staging)
+__device__ __forceinline__ uint4 opm_scale8(uint4 v, float w) {
+  uint32_t in[4] = {v.x, v.y, v.z, v.w}, o[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    o[k] = (uint32_t)f32_to_bf16_bits(bf16_bits_to_f32((uint16_t)(in[k] & 0xFFFFu)) * w) |
+           ((uint32_t)f32_to_bf16_bits(bf16_bits_to_f32((uint16_t)(in[k] >> 16)) * w) << 16);
+  return make_uint4(o[0], o[1], o[2], o[3]);
+}
+
 // ---------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------
+// WT: the result is multiplied by Wt[b, i, j] (fp32, (B, I, J)) instead of
+// by scale.  An accumulator fragment lies in one (i, j) pair, so that is one
+// scalar per fragment.
+template <bool WT>
 __global__ __launch_bounds__(256) void opm_fwd_kernel(
     uint16_t* __restrict__ O, const uint16_t* __restrict__ A,
     const uint16_t* __restrict__ Bm, int S, int I, int J, int nit, int njt,
-    float scale) {
+    float scale, const float* __restrict__ Wt) {
   __shared__ uint4 smem[F_SMEM];
   uint4* sA = smem;
   uint4* sB = smem + F_SLOTS;
@@ -225,8 +248,11 @@ __global__ __launch_bounds__(256) void opm_fwd_kernel(
       const int pi = wr * 2 + (m >> 1), pj = wc * 2 + (n >> 1);
       const int c = (m & 1) * 16 + lr;
       const int d = (n & 1) * 16 + lg * 4;
+      float sc = scale;
+      if (WT)  // clamped: the pairs past I or J are dropped at the store
+        sc = Wt[(bt * I + min(i0 + pi, I - 1)) * J + min(j0 + pj, J - 1)];
       *reinterpret_cast<uint2*>(sO + ((pi * OT + pj) * W + c) * OPITCH + d) =
-          opm_pack4(acc[m][n], scale);
+          opm_pack4(acc[m][n], sc);
     }
   __syncthreads();
   uint16_t* po = O + bt * ((int64_t)I * J * WW);
@@ -249,12 +275,17 @@ __global__ __launch_bounds__(256) void opm_fwd_kernel(
 // backward: out[b, s, p, m] = scale * sum_{q, k} T(p, q)[m, k] * X[b, s, q, k]
 // T(p, q) is the (c, d) tile of d_o at tile_p * p + tile_q * q; TR = false
 // takes it as [m = c][k = d] (da), TR = true as [m = d][k = c] (db).
+// WT: the weight Wt[b, i, j] (fp32, (B, I, J), addressed with the tile
+// strides / 1024) depends on (p, q), so it sits inside the K loop: every
+// d_o tile is multiplied by its weight on the way into LDS (bf16 -> fp32,
+// times w, one rounding back to bf16) and scale is 1.  The weight is loaded
+// with the tile, from the same clamped q; no weighted copy of d_o exists.
 // ---------------------------------------------------------------------------
-template <bool TR>
+template <bool TR, bool WT>
 __global__ __launch_bounds__(256) void opm_bwd_kernel(
     uint16_t* __restrict__ out, const uint16_t* __restrict__ dO,
     const uint16_t* __restrict__ X, int S, int P, int Q, int64_t tile_p,
-    int64_t tile_q, int nsc, float scale) {
+    int64_t tile_q, int nsc, float scale, const float* __restrict__ Wt) {
   __shared__ uint4 smem[B_SLOTS];
 
   int bid = blockIdx.x;
@@ -273,7 +304,16 @@ __global__ __launch_bounds__(256) void opm_bwd_kernel(
   // TR staging role: (q in step, 8-row group of c, 8-column group of d)
   const int tq = tid >> 4, tcg = (tid >> 2) & 3, tdg = tid & 3;
 
+  // weights of this p: one per q, at the tile strides in units of tiles
+  const float* wrow = nullptr;
+  int64_t w_q = 0;
+  if (WT) {
+    wrow = Wt + bt * ((int64_t)P * Q) + (int64_t)p * (tile_p / WW);
+    w_q = tile_q / WW;
+  }
+
   uint4 r[8];
+  float wv[TR ? 1 : 8];  // WT: the weight of r[j]'s tile (one q for all if TR)
   auto load_tiles = [&](int q0) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -282,11 +322,13 @@ __global__ __launch_bounds__(256) void opm_bwd_kernel(
         r[j] = opm_ld(tiles + (int64_t)min(q, Q - 1) * tile_q +
                           (tcg * 8 + j) * W + tdg * 8,
                       q < Q);
+        if (WT && j == 0) wv[0] = wrow[(int64_t)min(q, Q - 1) * w_q];
       } else {
         const int ch = j * 256 + tid;  // 16 B chunk of the step's 16 tiles
         const int q = q0 + (ch >> 7);
         r[j] = opm_ld(tiles + (int64_t)min(q, Q - 1) * tile_q + (ch & 127) * 8,
                       q < Q);
+        if (WT) wv[j] = wrow[(int64_t)min(q, Q - 1) * w_q];
       }
     }
   };
@@ -312,6 +354,10 @@ __global__ __launch_bounds__(256) void opm_bwd_kernel(
   load_tiles(0);
   for (int q0 = 0; q0 < Q; q0 += BQ) {
     __syncthreads();  // previous step's fragment reads are done
+    if (WT) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) r[j] = opm_scale8(r[j], wv[TR ? 0 : j]);
+    }
     if (TR) {
       uint4 t[8];
       opm_transpose8(r, t);
@@ -386,6 +432,19 @@ void opm_check_operand(const at::Tensor& t, const char* fn, const char* name,
               " data pointer is not 16-byte aligned");
 }
 
+// the weight of the *_w entries: fp32 (B, I, J), contiguous, next to ref
+void opm_check_weight(const at::Tensor& w, const at::Tensor& ref, int64_t B,
+                      int64_t I, int64_t J, const char* fn) {
+  TORCH_CHECK(w.is_cuda() && w.device() == ref.device(), fn,
+              ": w must be a CUDA tensor on the operands' device");
+  TORCH_CHECK(w.scalar_type() == at::kFloat, fn, ": w must be fp32 (got ",
+              w.scalar_type(), ")");
+  TORCH_CHECK(w.dim() == 3 && w.size(0) == B && w.size(1) == I && w.size(2) == J,
+              fn, ": w ", w.sizes(), " must be (B, I, J) = (", B, ", ", I, ", ",
+              J, ")");
+  TORCH_CHECK(w.is_contiguous(), fn, ": w must be contiguous");
+}
+
 // every factor is below 2^30 (opm_check_operand), so no product overflows
 unsigned opm_grid(int64_t n0, int64_t n1, int64_t n2, const char* fn) {
   const int64_t lim = (int64_t)1 << 31;
@@ -399,7 +458,7 @@ const uint16_t* cptr(const at::Tensor& t) {
 
 // shared body of the two gradients: x is b (for da) or a (for db)
 at::Tensor opm_backward(const at::Tensor& d_o, const at::Tensor& x, double scale,
-                        bool for_a, const char* fn) {
+                        bool for_a, const char* fn, const at::Tensor* w = nullptr) {
   opm_check_operand(d_o, fn, "d_o", 5);
   opm_check_operand(x, fn, for_a ? "b" : "a", 4);
   TORCH_CHECK(d_o.device() == x.device(), fn, ": operands on different devices");
@@ -409,6 +468,7 @@ at::Tensor opm_backward(const at::Tensor& d_o, const at::Tensor& x, double scale
   TORCH_CHECK(x.size(0) == B && x.size(2) == Q, fn, ": d_o ", d_o.sizes(), " and ",
               for_a ? "b " : "a ", x.sizes(), " must agree in B and ",
               for_a ? "J" : "I");
+  if (w) opm_check_weight(*w, d_o, B, I, J, fn);
   const int64_t nsc = (S + BS - 1) / BS;
   const unsigned grid = opm_grid(B, P, nsc, fn);
 
@@ -416,39 +476,64 @@ at::Tensor opm_backward(const at::Tensor& d_o, const at::Tensor& x, double scale
   auto out = at::empty({B, S, P, W}, d_o.options());
   auto stream = at::cuda::getCurrentCUDAStream();
   uint16_t* po = reinterpret_cast<uint16_t*>(out.data_ptr());
-  if (for_a)
-    opm_bwd_kernel<false><<<grid, 256, 0, stream>>>(
+  if (w) {
+    const float* pw = w->data_ptr<float>();
+    if (for_a)
+      opm_bwd_kernel<false, true><<<grid, 256, 0, stream>>>(
+          po, cptr(d_o), cptr(x), (int)S, (int)P, (int)Q, J * WW, (int64_t)WW,
+          (int)nsc, 1.0f, pw);
+    else
+      opm_bwd_kernel<true, true><<<grid, 256, 0, stream>>>(
+          po, cptr(d_o), cptr(x), (int)S, (int)P, (int)Q, (int64_t)WW, J * WW,
+          (int)nsc, 1.0f, pw);
+  } else if (for_a)
+    opm_bwd_kernel<false, false><<<grid, 256, 0, stream>>>(
         po, cptr(d_o), cptr(x), (int)S, (int)P, (int)Q, J * WW, (int64_t)WW,
-        (int)nsc, (float)scale);
+        (int)nsc, (float)scale, nullptr);
   else
-    opm_bwd_kernel<true><<<grid, 256, 0, stream>>>(
+    opm_bwd_kernel<true, false><<<grid, 256, 0, stream>>>(
         po, cptr(d_o), cptr(x), (int)S, (int)P, (int)Q, (int64_t)WW, J * WW,
-        (int)nsc, (float)scale);
+        (int)nsc, (float)scale, nullptr);
   C10_CUDA_KERNEL_LAUNCH_CHECK();
   return out;
 }
 
 }  // namespace
 
-at::Tensor opm_forward(at::Tensor a, at::Tensor b, double scale) {
-  const char* fn = "opm_forward";
+namespace {
+
+at::Tensor opm_forward_impl(const at::Tensor& a, const at::Tensor& b, double scale,
+                            const at::Tensor* w, const char* fn) {
   opm_check_operand(a, fn, "a", 4);
   opm_check_operand(b, fn, "b", 4);
   TORCH_CHECK(a.device() == b.device(), fn, ": a and b on different devices");
   const int64_t B = a.size(0), S = a.size(1), I = a.size(2), J = b.size(2);
   TORCH_CHECK(b.size(0) == B && b.size(1) == S, fn, ": a ", a.sizes(), " and b ",
               b.sizes(), " must agree in B and S");
+  if (w) opm_check_weight(*w, a, B, I, J, fn);
   const int64_t nit = (I + OT - 1) / OT, njt = (J + OT - 1) / OT;
   const unsigned grid = opm_grid(B, nit, njt, fn);
 
   c10::cuda::CUDAGuard guard(a.device());
   auto o = at::empty({B, I, J, W, W}, a.options());
   auto stream = at::cuda::getCurrentCUDAStream();
-  opm_fwd_kernel<<<grid, 256, 0, stream>>>(
-      reinterpret_cast<uint16_t*>(o.data_ptr()), cptr(a), cptr(b), (int)S, (int)I,
-      (int)J, (int)nit, (int)njt, (float)scale);
+  uint16_t* po = reinterpret_cast<uint16_t*>(o.data_ptr());
+  if (w)
+    opm_fwd_kernel<true><<<grid, 256, 0, stream>>>(
+        po, cptr(a), cptr(b), (int)S, (int)I, (int)J, (int)nit, (int)njt, 1.0f,
+        w->data_ptr<float>());
+  else
+    opm_fwd_kernel<false><<<grid, 256, 0, stream>>>(
+        po, cptr(a), cptr(b), (int)S, (int)I, (int)J, (int)nit, (int)njt,
+        (float)scale, nullptr);
   C10_CUDA_KERNEL_LAUNCH_CHECK();
   return o;
+}
+
+}  // namespace
+
+at::Tensor opm_forward(at::Tensor a, at::Tensor b, double scale) {
+  return opm_forward_impl(a, b, scale, nullptr, "opm_forward");
 }
 
 at::Tensor opm_backward_a(at::Tensor d_o, at::Tensor b, double scale) {
@@ -457,4 +542,18 @@ at::Tensor opm_backward_a(at::Tensor d_o, at::Tensor b, double scale) {
 
 at::Tensor opm_backward_b(at::Tensor d_o, at::Tensor a, double scale) {
   return opm_backward(d_o, a, scale, false, "opm_backward_b");
+}
+
+// the same three contractions with a per-pair weight w[b, i, j] in place of
+// the scalar scale (the reciprocal mask normaliser of a padded batch)
+at::Tensor opm_forward_w(at::Tensor a, at::Tensor b, at::Tensor w) {
+  return opm_forward_impl(a, b, 1.0, &w, "opm_forward_w");
+}
+
+at::Tensor opm_backward_a_w(at::Tensor d_o, at::Tensor b, at::Tensor w) {
+  return opm_backward(d_o, b, 1.0, true, "opm_backward_a_w", &w);
+}
+
+at::Tensor opm_backward_b_w(at::Tensor d_o, at::Tensor a, at::Tensor w) {
+  return opm_backward(d_o, a, 1.0, false, "opm_backward_b_w", &w);
 }

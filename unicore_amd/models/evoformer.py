@@ -38,6 +38,7 @@ from unicore_amd.modules import (
 )
 from unicore_amd.modules.dropout_add_ln import dropout_add_ln_pre
 from unicore_amd.modules.embedding import Embedding
+from unicore_amd.modules.padding_mask import build_evoformer_masks
 from unicore_amd.modules.triangle_attention import TriangleAttention
 
 
@@ -67,7 +68,9 @@ class MSARowAttentionWithPairBias(nn.Module):
         self.dropout = dropout
         self.scaling = self.head_dim**-0.5
 
-    def forward(self, msa, pair, skip_out_bias=False, x_normed=None):
+    def forward(self, msa, pair, skip_out_bias=False, x_normed=None,
+                key_mask=None):
+        # key_mask: additive (B, 1, S, 1, L), padded residues as keys
         B, S, L, D = msa.shape
         H, Dh = self.heads, self.head_dim
         x = self.norm(msa) if x_normed is None else x_normed
@@ -84,7 +87,8 @@ class MSARowAttentionWithPairBias(nn.Module):
         scores = qk_scores(q, k).view(B, H, S, L, L)
         bias = self.pair_bias(self.pair_norm(pair))  # (B, L, L, H)
         bias = bias.permute(0, 3, 1, 2).unsqueeze(2)  # (B, H, 1, L, L)
-        attn = softmax_dropout(scores, self.dropout, self.training, bias=bias)
+        attn = softmax_dropout(scores, self.dropout, self.training,
+                               mask=key_mask, bias=bias)
         o = torch.bmm(attn.view(B * H * S, L, L), v)
         o = msa_merge(o, B, S, L, H, col=False)
         if _fold_ok(self.gate.bias):
@@ -109,7 +113,8 @@ class MSAColumnAttention(nn.Module):
         self.dropout = dropout
         self.scaling = self.head_dim**-0.5
 
-    def forward(self, msa, skip_out_bias=False, x_normed=None):
+    def forward(self, msa, skip_out_bias=False, x_normed=None, key_mask=None):
+        # key_mask: additive (B, L, 1, 1, S), padded MSA rows as keys
         B, S, L, D = msa.shape
         H, Dh = self.heads, self.head_dim
         x = self.norm(msa) if x_normed is None else x_normed
@@ -123,7 +128,13 @@ class MSAColumnAttention(nn.Module):
         k = arrange(k)
         v = arrange(v)
         scores = qk_scores(q, k).view(B * L * H, S, S)
-        attn = softmax_dropout(scores, self.dropout, self.training)
+        if key_mask is None:
+            attn = softmax_dropout(scores, self.dropout, self.training)
+        else:
+            # msa_arrange(col=True) orders the batches (B, L, H)
+            attn = softmax_dropout(scores.view(B, L, H, S, S), self.dropout,
+                                   self.training, mask=key_mask)
+            attn = attn.view(B * L * H, S, S)
         o = torch.bmm(attn, v)
         o = msa_merge(o, B, S, L, H, col=True)
         if _fold_ok(self.gate.bias):
@@ -173,11 +184,14 @@ class OuterProductMean(nn.Module):
         self.out = nn.Linear(c * c, d_pair)
         self.c = c
 
-    def forward(self, msa, skip_out_bias=False, x_normed=None):
+    def forward(self, msa, skip_out_bias=False, x_normed=None, mask=None,
+                inv_norm=None):
+        # mask: 0/1 (B, S, L); inv_norm: its opm_mask_inv_norm, (B, L, L)
         x = self.norm(msa) if x_normed is None else x_normed
         a = self.a(x)  # (B, S, L, c)
         b = self.b(x)
-        o = outer_product_mean(a, b)  # (B, L, L, c*c), mean over S
+        # (B, L, L, c*c), mean over S (over the real rows under a mask)
+        o = outer_product_mean(a, b, mask=mask, inv_norm=inv_norm)
         if skip_out_bias:
             return F.linear(o, self.out.weight)
         return self.out(o)
@@ -196,19 +210,26 @@ class TriangleMultiplication(nn.Module):
         self.gate = nn.Linear(d_pair, d_pair)
         self.outgoing = outgoing
 
-    def forward(self, pair, p_normed=None):
+    def forward(self, pair, p_normed=None, pair_mask=None):
+        # pair_mask: 0/1 (B, I, J), multiplies a and b after gating so the
+        # contraction skips padded k
         p = self.norm(pair) if p_normed is None else p_normed
         if _fold_ok(self.a_proj.bias, self.a_gate.bias, self.b_proj.bias,
                     self.b_gate.bias, self.out.bias, self.gate.bias):
             a = gated_mul(F.linear(p, self.a_proj.weight),
                           F.linear(p, self.a_gate.weight),
-                          self.a_proj.bias, self.a_gate.bias)
+                          self.a_proj.bias, self.a_gate.bias,
+                          row_mask=pair_mask)
             b = gated_mul(F.linear(p, self.b_proj.weight),
                           F.linear(p, self.b_gate.weight),
-                          self.b_proj.bias, self.b_gate.bias)
+                          self.b_proj.bias, self.b_gate.bias,
+                          row_mask=pair_mask)
         else:
             a = self.a_proj(p) * torch.sigmoid(self.a_gate(p))  # (B, I, J, c)
             b = self.b_proj(p) * torch.sigmoid(self.b_gate(p))
+            if pair_mask is not None:
+                a = a * pair_mask.unsqueeze(-1)
+                b = b * pair_mask.unsqueeze(-1)
         o = triangle_multiply(a, b, self.outgoing)
         if _fold_ok(self.out.bias, self.gate.bias):
             return gated_mul(F.linear(self.out_norm(o), self.out.weight),
@@ -251,7 +272,18 @@ class EvoformerBlock(nn.Module):
             return dropout_add(y, residual, p, True, shared_dim=shared_dim)
         return residual + y
 
-    def forward(self, msa, pair):
+    def forward(self, msa, pair, masks=None):
+        """masks: optional padding_mask.EvoformerMasks of a padded batch."""
+        # keyword arguments of the masked sub-modules; empty without masks,
+        # so that every call is then the one it has always been
+        k_row = k_col = k_opm = k_tri = k_start = k_end = {}
+        if masks is not None:
+            k_row = {"key_mask": masks.row_key}
+            k_col = {"key_mask": masks.col_key}
+            k_opm = {"mask": masks.msa, "inv_norm": masks.opm_inv_norm}
+            k_tri = {"pair_mask": masks.pair}
+            k_start = {"key_mask": masks.tri_start_key}
+            k_end = {"key_mask": masks.tri_end_key}
         fold = msa.is_cuda and _fold_ok(
             self.row_attn.out.bias, self.col_attn.out.bias,
             self.msa_transition.fc1.bias, self.msa_transition.fc2.bias,
@@ -275,31 +307,35 @@ class EvoformerBlock(nn.Module):
             prow = 1 if pd > 0 else None
             pcol = 2 if pd > 0 else None
             n = self.row_attn.norm(msa)
-            y = self.row_attn(msa, pair, skip_out_bias=True, x_normed=n)
+            y = self.row_attn(msa, pair, skip_out_bias=True, x_normed=n,
+                              **k_row)
             msa, n = dropout_add_ln_pre(y, msa, self.col_attn.norm, md, t,
                                         bias=self.row_attn.out.bias,
                                         shared_dim=mrow)
-            y = self.col_attn(msa, skip_out_bias=True, x_normed=n)
+            y = self.col_attn(msa, skip_out_bias=True, x_normed=n,
+                              **k_col)
             msa, n = dropout_add_ln_pre(y, msa, self.msa_transition.norm, 0.0,
                                         t, bias=self.col_attn.out.bias)
             y = self.msa_transition.tail(n)
             msa, n = dropout_add_ln_pre(y, msa, self.opm.norm, 0.0, t,
                                         bias=self.msa_transition.fc2.bias)
-            y = self.opm(msa, skip_out_bias=True, x_normed=n)
+            y = self.opm(msa, skip_out_bias=True, x_normed=n, **k_opm)
             pair, pn = dropout_add_ln_pre(y, pair, self.tri_out.norm, 0.0, t,
                                           bias=self.opm.out.bias)
-            y = self.tri_out(pair, p_normed=pn)
+            y = self.tri_out(pair, p_normed=pn, **k_tri)
             pair, pn = dropout_add_ln_pre(y, pair, self.tri_in.norm, pd, t,
                                           shared_dim=prow)
-            y = self.tri_in(pair, p_normed=pn)
+            y = self.tri_in(pair, p_normed=pn, **k_tri)
             if self.triangle_attention:
                 pair, pn = dropout_add_ln_pre(y, pair, self.tri_att_start.norm,
                                               pd, t, shared_dim=prow)
-                y = self.tri_att_start(pair, skip_out_bias=True, p_normed=pn)
+                y = self.tri_att_start(pair, skip_out_bias=True, p_normed=pn,
+                                       **k_start)
                 pair, pn = dropout_add_ln_pre(
                     y, pair, self.tri_att_end.norm, pd, t,
                     bias=self.tri_att_start.out.bias, shared_dim=prow)
-                y = self.tri_att_end(pair, skip_out_bias=True, p_normed=pn)
+                y = self.tri_att_end(pair, skip_out_bias=True, p_normed=pn,
+                                     **k_end)
                 pair, pn = dropout_add_ln_pre(
                     y, pair, self.pair_transition.norm, pd, t,
                     bias=self.tri_att_end.out.bias, shared_dim=pcol)
@@ -311,16 +347,19 @@ class EvoformerBlock(nn.Module):
             pair = dropout_add(y, pair, 0.0, t,
                                bias=self.pair_transition.fc2.bias)
             return msa, pair
-        msa = self._join(self.row_attn(msa, pair), msa, self.msa_dropout, 1)
-        msa = msa + self.col_attn(msa)
+        msa = self._join(self.row_attn(msa, pair, **k_row), msa,
+                         self.msa_dropout, 1)
+        msa = msa + self.col_attn(msa, **k_col)
         msa = self.msa_transition(msa, residual=msa)
-        pair = pair + self.opm(msa)
-        pair = self._join(self.tri_out(pair), pair, self.pair_dropout, 1)
-        pair = self._join(self.tri_in(pair), pair, self.pair_dropout, 1)
+        pair = pair + self.opm(msa, **k_opm)
+        pair = self._join(self.tri_out(pair, **k_tri), pair,
+                          self.pair_dropout, 1)
+        pair = self._join(self.tri_in(pair, **k_tri), pair,
+                          self.pair_dropout, 1)
         if self.triangle_attention:
-            pair = self._join(self.tri_att_start(pair), pair,
-                              self.pair_dropout, 1)
-            pair = self._join(self.tri_att_end(pair), pair,
+            pair = self._join(self.tri_att_start(pair, **k_start),
+                              pair, self.pair_dropout, 1)
+            pair = self._join(self.tri_att_end(pair, **k_end), pair,
                               self.pair_dropout, 2)
         pair = self.pair_transition(pair, residual=pair)
         return msa, pair
@@ -361,6 +400,13 @@ class EvoformerModel(BaseUnicoreModel):
                                  "multiplication and the pair transition")
         parser.add_argument("--tri-attn-heads", type=int, metavar="N",
                             help="heads of the triangle attention modules")
+        parser.add_argument("--msa-padding-mask", action="store_true",
+                            help="derive a padding mask from src_tokens "
+                                 "(1 where a token is not pad) and mask the "
+                                 "row/column/triangle attention keys, the "
+                                 "outer-product mean and the triangle "
+                                 "multiplications with it, so that ragged "
+                                 "MSAs can be batched with padding")
         parser.add_argument("--hip-graph-blocks", action="store_true",
                             help="capture each Evoformer block as a hipGraph "
                                  "(fwd+bwd) and replay it — removes the "
@@ -397,6 +443,12 @@ class EvoformerModel(BaseUnicoreModel):
         self.activation_checkpoint = args.activation_checkpoint
         self.hip_graph_blocks = getattr(args, "hip_graph_blocks", False)
         self._graphed_blocks = None
+        self.msa_padding_mask = getattr(args, "msa_padding_mask", False)
+        assert not (self.msa_padding_mask and self.hip_graph_blocks), (
+            "--hip-graph-blocks and --msa-padding-mask are mutually "
+            "exclusive: the masks change with every batch, a captured graph "
+            "would replay the ones it was captured with"
+        )
 
     @classmethod
     def build_model(cls, args, task):
@@ -443,25 +495,35 @@ class EvoformerModel(BaseUnicoreModel):
             )
         return self._graphed_blocks(msa, pair)
 
-    def _trunk(self, msa, pair):
+    def _trunk(self, msa, pair, masks=None):
         if self.hip_graph_blocks and msa.is_cuda:
+            assert masks is None, "--hip-graph-blocks takes no padding masks"
             return self._graphed_trunk(msa, pair)
         if self.activation_checkpoint and self.training:
             # recompute each block in backward; the msa/pair pair threads
-            # through as the tuple state (utils.checkpoint_sequential)
+            # through as the tuple state (utils.checkpoint_sequential), the
+            # masks (no gradient) ride the closures
             fns = [
-                (lambda b: (lambda m, p: b(m, p)))(blk) for blk in self.blocks
+                (lambda b: (lambda m, p: b(m, p, masks)))(blk)
+                for blk in self.blocks
             ]
             msa, pair = utils.checkpoint_sequential(fns, (msa, pair))
         else:
             for blk in self.blocks:
-                msa, pair = blk(msa, pair)
+                msa, pair = blk(msa, pair, masks)
         return msa, pair
 
-    def forward(self, src_tokens, **kwargs):
-        # src_tokens: (B, S, L)
+    def forward(self, src_tokens, msa_mask=None, **kwargs):
+        # src_tokens: (B, S, L); msa_mask: optional (B, S, L), 1 = real token
         B, S, L = src_tokens.shape
         msa = self.embed_msa(src_tokens)
+        masks = None
+        if self.msa_padding_mask or msa_mask is not None:
+            # always derived under the flag: testing it for padding first
+            # would be a device sync
+            if msa_mask is None:
+                msa_mask = src_tokens.ne(self.padding_idx)
+            masks = build_evoformer_masks(msa_mask, msa.dtype)
         pos = torch.arange(L, device=src_tokens.device)
         rel = (pos[None, :] - pos[:, None]).clamp(-self.max_rel, self.max_rel)
         pair = self.rel_pos_embed(rel + self.max_rel)  # (L, L, Dp)
@@ -471,8 +533,8 @@ class EvoformerModel(BaseUnicoreModel):
         # representations; only the final pass builds the autograd graph
         for _ in range(self.recycle_iters):
             with torch.no_grad():
-                msa, pair = self._trunk(msa, pair)
-        msa, pair = self._trunk(msa, pair)
+                msa, pair = self._trunk(msa, pair, masks)
+        msa, pair = self._trunk(msa, pair, masks)
         return self.lm_head(self.final_norm(msa))
 
 
@@ -489,5 +551,6 @@ def evoformer_base_architecture(args):
     args.recycle_iters = getattr(args, "recycle_iters", None) or 0
     args.activation_checkpoint = getattr(args, "activation_checkpoint", False)
     args.hip_graph_blocks = getattr(args, "hip_graph_blocks", False)
+    args.msa_padding_mask = getattr(args, "msa_padding_mask", False)
     args.triangle_attention = getattr(args, "triangle_attention", False)
     args.tri_attn_heads = getattr(args, "tri_attn_heads", None) or 4

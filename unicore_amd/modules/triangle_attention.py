@@ -37,6 +37,7 @@ import torch.nn.functional as F
 from .gated_mul import gated_mul
 from .layer_norm import LayerNorm
 from .multihead_attention import qk_scores
+from .padding_mask import triangle_key_mask
 from .softmax_dropout import softmax_dropout
 
 # default of the UNICORE_TRIATTN_FUSED gate: off (opt-in). Same-box figures
@@ -239,7 +240,11 @@ class TriangleAttention(nn.Module):
         self.starting = starting
         self.scaling = self.head_dim**-0.5
 
-    def forward(self, pair, skip_out_bias=False, p_normed=None):
+    def forward(self, pair, skip_out_bias=False, p_normed=None,
+                pair_mask=None, key_mask=None):
+        """pair_mask: optional 0/1 (B, I, J) padding mask; its additive key
+        mask (padding_mask.triangle_key_mask) may be passed as ``key_mask``
+        by a caller that builds it once for many blocks."""
         B, I, J, C = pair.shape
         H, D = self.heads, self.head_dim
         tr = not self.starting
@@ -253,7 +258,10 @@ class TriangleAttention(nn.Module):
         q = q * self.scaling
         scores = qk_scores(q, k).view(B, H, R, T, T)
         bias = pair_bias_arrange(self.bias_proj(p), tr).unsqueeze(2)
-        attn = softmax_dropout(scores, self.dropout, self.training, bias=bias)
+        if key_mask is None and pair_mask is not None:
+            key_mask = triangle_key_mask(pair_mask, scores.dtype, self.starting)
+        attn = softmax_dropout(scores, self.dropout, self.training,
+                               mask=key_mask, bias=bias)
         o = torch.bmm(attn.view(B * H * R, T, T), v)
         o = pair_merge(o, B, I, J, H, tr)
         if _fold_ok(self.gate.bias):

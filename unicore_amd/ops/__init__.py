@@ -336,6 +336,18 @@ def gated_mul_bwd(grad, x, g, bias_x=None, bias_g=None):
     return _kernels.gated_mul_backward(grad, x, g, bias_x, bias_g)
 
 
+def gated_mul_masked_fwd(x, g, bias_x, bias_g, row_mask):
+    # out[r, :] = (x[r, :] + bias_x) * sigmoid(g[r, :] + bias_g) * row_mask[r]
+    require_kernels()
+    return _kernels.gated_mul_masked_forward(x, g, bias_x, bias_g, row_mask)
+
+
+def gated_mul_masked_bwd(grad, x, g, bias_x, bias_g, row_mask):
+    require_kernels()
+    return _kernels.gated_mul_masked_backward(grad, x, g, bias_x, bias_g,
+                                              row_mask)
+
+
 def msa_arrange(x, B, S, L, heads, col, inverse=False):
     # (B,S,L,E) <-> head-major MSA layouts; see modules/msa_arrange.py
     require_kernels()
@@ -377,6 +389,24 @@ def opm_bwd_b(d_o, a, scale):
     """db[b,s,j,d] = scale * sum_{i,c} d_o[b,i,j,c,d] * a[b,s,i,c]."""
     require_kernels()
     return _kernels.opm_backward_b(d_o, a, float(scale))
+
+
+def opm_fwd_w(a, b, w):
+    """opm_fwd with w[b,i,j] (contiguous fp32 (B,I,J)) in place of scale."""
+    require_kernels()
+    return _kernels.opm_forward_w(a, b, w)
+
+
+def opm_bwd_a_w(d_o, b, w):
+    """da[b,s,i,c] = sum_{j,d} w[b,i,j] * d_o[b,i,j,c,d] * b[b,s,j,d]."""
+    require_kernels()
+    return _kernels.opm_backward_a_w(d_o, b, w)
+
+
+def opm_bwd_b_w(d_o, a, w):
+    """db[b,s,j,d] = sum_{i,c} w[b,i,j] * d_o[b,i,j,c,d] * a[b,s,i,c]."""
+    require_kernels()
+    return _kernels.opm_backward_b_w(d_o, a, w)
 
 
 def opm_supported(c, d, dtype) -> bool:
