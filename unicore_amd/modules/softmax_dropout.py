@@ -101,9 +101,7 @@ class SoftmaxDropoutFast(torch.autograd.Function):
             n_batch, q, k = softmax_results.shape
             bb, bq, _ = ctx.bias_shape
             od = ctx.bias_outer_div
-            if softmax_results.is_cuda and ops.softmax_dropout_bwd_bias_supported(
-                n_batch, q, k, bb, bq, od
-            ):
+            if ops.softmax_dropout_bwd_bias_supported(n_batch, q, k, bb, bq, od):
                 # fused: the backward kernel accumulates the bias grad
                 # while it writes grad_input, instead of re-reading the
                 # whole grad tensor for the eager .sum
@@ -154,7 +152,6 @@ def softmax_dropout(
 
     Shapes: inputs (..., q, k); mask/bias broadcastable to inputs.
     """
-    input_shape = inputs.shape
     use_kernel = False
     if inputs.is_cuda:
         from unicore_amd import ops
@@ -165,7 +162,16 @@ def softmax_dropout(
 
     if not use_kernel:
         return _eager_softmax_dropout(inputs, dropout_prob, is_training, mask, bias)
+    return _kernel_softmax_dropout(
+        inputs, dropout_prob, is_training, mask, bias, inplace
+    )
 
+
+def _kernel_softmax_dropout(inputs, dropout_prob, is_training, mask, bias, inplace):
+    """The kernel route of ``softmax_dropout``: flatten to (n_batch, q, k),
+    describe (or eagerly merge) mask and bias, call the fused op. Split out
+    so the CPU suite can drive it against a stand-in for ``ops``."""
+    input_shape = inputs.shape
     inputs = inputs.contiguous()
     if not inplace:
         inputs = inputs.clone()
@@ -184,19 +190,21 @@ def softmax_dropout(
     if bias is not None:
         bias_k, bias_od, inputs_3d = _prep_additive(bias, inputs_3d, batch_dims, q, k)
 
-    if k <= 4096:
+    drop = is_training and dropout_prob > 0
+    if not drop or (k <= 4096 and k % 8 == 0):
         out = SoftmaxDropoutFast.apply(
             is_training, inputs_3d, mask_k, mask_od, bias_k, bias_od, dropout_prob
         )
     else:
-        # very wide rows: fused softmax (p=0) via the LDS block kernel,
-        # separate torch dropout (reference routes the same way,
+        # very wide rows, or a width that is no multiple of 8: the kernel's
+        # dropout needs whole 8-element vectors, so these take the fused
+        # softmax (p=0) via the block kernel and a separate torch dropout
+        # (reference routes wide rows the same way,
         # unicore/modules/softmax_dropout.py:131-138)
         out = SoftmaxDropoutFast.apply(
             is_training, inputs_3d, mask_k, mask_od, bias_k, bias_od, 0.0
         )
-        if is_training and dropout_prob > 0:
-            out = F.dropout(out, p=dropout_prob)
+        out = F.dropout(out, p=dropout_prob)
     return out.view(input_shape)
 
 
