@@ -6,6 +6,7 @@
 // per-row LSE in one pass (dx = g * (softmax - onehot)).  fp32 math
 // internally, bf16/fp16/fp32 logits.
 #include "common.h"
+#include "dispatch.h"
 
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
@@ -132,27 +133,6 @@ __global__ void ce_bwd_kernel(T* __restrict__ dx, const T* __restrict__ logits,
     }
   }
 }
-
-#define DISPATCH_FTYPES(st, NAME, ...)                               \
-  switch (st) {                                                      \
-    case at::ScalarType::Float: {                                    \
-      using scalar_t = float;                                        \
-      __VA_ARGS__;                                                   \
-      break;                                                         \
-    }                                                                \
-    case at::ScalarType::Half: {                                     \
-      using scalar_t = __half;                                       \
-      __VA_ARGS__;                                                   \
-      break;                                                         \
-    }                                                                \
-    case at::ScalarType::BFloat16: {                                 \
-      using scalar_t = __hip_bfloat16;                               \
-      __VA_ARGS__;                                                   \
-      break;                                                         \
-    }                                                                \
-    default:                                                         \
-      TORCH_CHECK(false, NAME, ": unsupported dtype ", st);          \
-  }
 
 }  // namespace
 

@@ -7,6 +7,7 @@
 // NOTE: atomic accumulation order is non-deterministic; callers fall back to
 // the torch path when torch.use_deterministic_algorithms is on.
 #include "common.h"
+#include "dispatch.h"
 
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
@@ -69,27 +70,6 @@ __global__ void f32_to_t_kernel(T* __restrict__ out, const float* __restrict__ i
       if (i0 + j < n) out[i0 + j] = Cvt<T>::from_f(in[i0 + j]);
   }
 }
-
-#define DISPATCH_FTYPES(st, NAME, ...)                               \
-  switch (st) {                                                      \
-    case at::ScalarType::Float: {                                    \
-      using scalar_t = float;                                        \
-      __VA_ARGS__;                                                   \
-      break;                                                         \
-    }                                                                \
-    case at::ScalarType::Half: {                                     \
-      using scalar_t = __half;                                       \
-      __VA_ARGS__;                                                   \
-      break;                                                         \
-    }                                                                \
-    case at::ScalarType::BFloat16: {                                 \
-      using scalar_t = __hip_bfloat16;                               \
-      __VA_ARGS__;                                                   \
-      break;                                                         \
-    }                                                                \
-    default:                                                         \
-      TORCH_CHECK(false, NAME, ": unsupported dtype ", st);          \
-  }
 
 }  // namespace
 

@@ -14,6 +14,7 @@
 // thread's 8 elements lie in one row (C % 8 == 0), so m costs one scalar
 // load per 16 B of x.  MASK = false compiles to the kernels as they were.
 #include "common.h"
+#include "dispatch.h"
 #include "fold.h"
 
 #include <torch/extension.h>
@@ -23,27 +24,6 @@
 #include <vector>
 
 namespace {
-
-#define DISPATCH_FTYPES(st, NAME, ...)                               \
-  switch (st) {                                                      \
-    case at::ScalarType::Float: {                                    \
-      using scalar_t = float;                                        \
-      __VA_ARGS__;                                                   \
-      break;                                                         \
-    }                                                                \
-    case at::ScalarType::Half: {                                     \
-      using scalar_t = __half;                                       \
-      __VA_ARGS__;                                                   \
-      break;                                                         \
-    }                                                                \
-    case at::ScalarType::BFloat16: {                                 \
-      using scalar_t = __hip_bfloat16;                               \
-      __VA_ARGS__;                                                   \
-      break;                                                         \
-    }                                                                \
-    default:                                                         \
-      TORCH_CHECK(false, NAME, ": unsupported dtype ", st);          \
-  }
 
 __device__ __forceinline__ float sigmoidf_(float v) {
   return 1.0f / (1.0f + __expf(-v));

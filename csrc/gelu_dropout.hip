@@ -6,10 +6,7 @@
 // per 8-element vector, same contract as the softmax_dropout kernel);
 // backward recomputes gelu'(x) from the saved input.
 #include "common.h"
-
-#include <torch/extension.h>
-#include <ATen/cuda/CUDAContext.h>
-#include <ATen/cuda/CUDAGeneratorImpl.h>
+#include "dispatch.h"
 
 #include <optional>
 #include <vector>
@@ -33,7 +30,7 @@ __global__ void gelu_dropout_fwd_kernel(T* __restrict__ out,
                                         const T* __restrict__ bias, int C,
                                         int64_t n8,
                                         float pinv, uint32_t pthresh,
-                                        uint64_t seed, uint64_t offset) {
+                                        uint64_t rngkey) {
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = tid; i < n8; i += stride) {
@@ -49,8 +46,7 @@ __global__ void gelu_dropout_fwd_kernel(T* __restrict__ out,
     for (int j = 0; j < 8; ++j) f[j] = gelu_fwd(f[j]);
     if constexpr (DROP) {
       bool keep[8];
-      keep16x8(seed + offset * 0x9E3779B97F4A7C15ull, (uint64_t)i, 0, pthresh,
-               keep);
+      keep16x8(rngkey, (uint64_t)i, 0, pthresh, keep);
       uint8_t bits = 0;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
@@ -106,27 +102,6 @@ __global__ void gelu_dropout_bwd_kernel(T* __restrict__ dx, const T* __restrict_
   }
 }
 
-#define DISPATCH_FTYPES(st, NAME, ...)                               \
-  switch (st) {                                                      \
-    case at::ScalarType::Float: {                                    \
-      using scalar_t = float;                                        \
-      __VA_ARGS__;                                                   \
-      break;                                                         \
-    }                                                                \
-    case at::ScalarType::Half: {                                     \
-      using scalar_t = __half;                                       \
-      __VA_ARGS__;                                                   \
-      break;                                                         \
-    }                                                                \
-    case at::ScalarType::BFloat16: {                                 \
-      using scalar_t = __hip_bfloat16;                               \
-      __VA_ARGS__;                                                   \
-      break;                                                         \
-    }                                                                \
-    default:                                                         \
-      TORCH_CHECK(false, NAME, ": unsupported dtype ", st);          \
-  }
-
 }  // namespace
 
 std::vector<at::Tensor> gelu_dropout_forward(at::Tensor x,
@@ -137,26 +112,15 @@ std::vector<at::Tensor> gelu_dropout_forward(at::Tensor x,
   const int64_t n8 = x.numel() / 8;
   const bool drop = is_training && p > 0.0;
   auto out = at::empty_like(x);
-  at::Tensor dmask;
+  auto dmask = at::empty({drop ? n8 : 0}, x.options().dtype(at::kByte));
   float pinv = 1.f;
   uint32_t pthresh = 0;
-  uint64_t seed = 0, offset = 0;
+  uint64_t rngkey = 0;
   if (drop) {
-    dmask = at::empty({n8}, x.options().dtype(at::kByte));
     const double pc = std::min(p, 0.999999);
     pinv = (float)(1.0 / (1.0 - pc));
     pthresh = keep16_threshold(pc);
-    auto gen = at::get_generator_or_default<at::CUDAGeneratorImpl>(
-        std::nullopt, at::cuda::detail::getDefaultCUDAGenerator());
-    at::PhiloxCudaState state;
-    {
-      std::lock_guard<std::mutex> lock(gen->mutex_);
-      state = gen->philox_cuda_state(4 + n8 / (2048LL * 256) * 2);
-    }
-    seed = state.seed_.val;
-    offset = state.offset_.val;
-  } else {
-    dmask = at::empty({0}, x.options().dtype(at::kByte));
+    rngkey = reserve_dropout_key(n8);
   }
   const bool has_bias = bias.has_value();
   at::Tensor bc;
@@ -179,7 +143,7 @@ std::vector<at::Tensor> gelu_dropout_forward(at::Tensor x,
           DROP ? dmask.data_ptr<uint8_t>() : nullptr,
           reinterpret_cast<const scalar_t*>(x.data_ptr()),
           HB ? reinterpret_cast<const scalar_t*>(bc.data_ptr()) : nullptr, C,
-          n8, pinv, pthresh, seed, offset);
+          n8, pinv, pthresh, rngkey);
     };
     if (drop) {
       if (has_bias) launch(std::true_type{}, std::true_type{});

@@ -11,6 +11,7 @@
 //    in registers (coalesced column-strided loads), stage 2 reduces the
 //    partials.  No atomics, bitwise-reproducible.
 #include "common.h"
+#include "dispatch.h"
 
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
@@ -18,27 +19,6 @@
 #include <vector>
 
 namespace {
-
-#define DISPATCH_FTYPES(st, NAME, ...)                               \
-  switch (st) {                                                      \
-    case at::ScalarType::Float: {                                    \
-      using scalar_t = float;                                        \
-      __VA_ARGS__;                                                   \
-      break;                                                         \
-    }                                                                \
-    case at::ScalarType::Half: {                                     \
-      using scalar_t = __half;                                       \
-      __VA_ARGS__;                                                   \
-      break;                                                         \
-    }                                                                \
-    case at::ScalarType::BFloat16: {                                 \
-      using scalar_t = __hip_bfloat16;                               \
-      __VA_ARGS__;                                                   \
-      break;                                                         \
-    }                                                                \
-    default:                                                         \
-      TORCH_CHECK(false, NAME, ": unsupported dtype ", st);          \
-  }
 
 // ---------------------------------------------------------------------------
 // forward

@@ -8,6 +8,7 @@
 // Same HBM traffic as one pass (16 B/lane vectors); kills the separate
 // q-scale sweep, the torch cat kernel and 5 extra launches per layer.
 #include "common.h"
+#include "dispatch.h"
 #include "fold.h"
 
 #include <torch/extension.h>
@@ -101,27 +102,6 @@ __global__ void qkv_split_bwd_kernel(T* __restrict__ dqkv, const T* __restrict__
                       partials + (int64_t)blockIdx.x * C);
   }
 }
-
-#define DISPATCH_FTYPES(st, NAME, ...)                               \
-  switch (st) {                                                      \
-    case at::ScalarType::Float: {                                    \
-      using scalar_t = float;                                        \
-      __VA_ARGS__;                                                   \
-      break;                                                         \
-    }                                                                \
-    case at::ScalarType::Half: {                                     \
-      using scalar_t = __half;                                       \
-      __VA_ARGS__;                                                   \
-      break;                                                         \
-    }                                                                \
-    case at::ScalarType::BFloat16: {                                 \
-      using scalar_t = __hip_bfloat16;                               \
-      __VA_ARGS__;                                                   \
-      break;                                                         \
-    }                                                                \
-    default:                                                         \
-      TORCH_CHECK(false, NAME, ": unsupported dtype ", st);          \
-  }
 
 }  // namespace
 

@@ -17,6 +17,7 @@
 // mask/bias broadcast contract (see unicore_amd/modules/softmax_dropout.py):
 // source row = ((b / outer_div) % src_nb) * src_q + (q % src_q).
 #include "common.h"
+#include "dispatch.h"
 
 #include <cstdlib>
 
@@ -389,27 +390,6 @@ __global__ void softmax_bwd_block_kernel(T* __restrict__ g, const T* __restrict_
     __syncthreads();
   }
 }
-
-#define DISPATCH_FTYPES(st, NAME, ...)                               \
-  switch (st) {                                                      \
-    case at::ScalarType::Float: {                                    \
-      using scalar_t = float;                                        \
-      __VA_ARGS__;                                                   \
-      break;                                                         \
-    }                                                                \
-    case at::ScalarType::Half: {                                     \
-      using scalar_t = __half;                                       \
-      __VA_ARGS__;                                                   \
-      break;                                                         \
-    }                                                                \
-    case at::ScalarType::BFloat16: {                                 \
-      using scalar_t = __hip_bfloat16;                               \
-      __VA_ARGS__;                                                   \
-      break;                                                         \
-    }                                                                \
-    default:                                                         \
-      TORCH_CHECK(false, NAME, ": unsupported dtype ", st);          \
-  }
 
 struct SrcDesc {
   const void* ptr = nullptr;

@@ -46,6 +46,7 @@
 //     Both sides see full lines; a flat order would leave one side with
 //     64 scattered 16 B pieces per instruction.
 #include "common.h"
+#include "dispatch.h"
 
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
@@ -55,27 +56,6 @@
 #include <type_traits>
 
 namespace {
-
-#define DISPATCH_FTYPES(st, NAME, ...)                               \
-  switch (st) {                                                      \
-    case at::ScalarType::Float: {                                    \
-      using scalar_t = float;                                        \
-      __VA_ARGS__;                                                   \
-      break;                                                         \
-    }                                                                \
-    case at::ScalarType::Half: {                                     \
-      using scalar_t = __half;                                       \
-      __VA_ARGS__;                                                   \
-      break;                                                         \
-    }                                                                \
-    case at::ScalarType::BFloat16: {                                 \
-      using scalar_t = __hip_bfloat16;                               \
-      __VA_ARGS__;                                                   \
-      break;                                                         \
-    }                                                                \
-    default:                                                         \
-      TORCH_CHECK(false, NAME, ": unsupported dtype ", st);          \
-  }
 
 // strided (B, I, J, C) <-> head-major (B, H, R, T, D), in 16 B units.
 // `sd` is the strided side with unit strides (sb, sr, st, 1), `hm` the

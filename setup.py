@@ -39,7 +39,6 @@ HIP_SOURCES = [
     "csrc/triangle.hip",
     "csrc/outer_product.hip",
     "csrc/tri_attn.hip",
-    "csrc/shared_dropout.hip",
 ]
 
 setup(

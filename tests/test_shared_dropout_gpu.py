@@ -1,7 +1,8 @@
-"""Shared-axis dropout of the fused residual joins on the GPU
-(csrc/shared_dropout.hip): mask sharing and storage, keep rate, values,
-backward, determinism, fallbacks, host checks, the Evoformer joins and the
-trainer.
+"""Shared-axis dropout of the fused residual joins on the GPU (the join
+kernels of csrc/dropout_add.hip and csrc/dropout_add_ln.hip with the shared
+mask map of csrc/dropout_mask.h): mask sharing and storage, keep rate,
+values, backward, determinism, the keying shared with the flat map,
+fallbacks, host checks, the Evoformer joins and the trainer.
 
 Shapes are the smallest that reach every branch: odd R and T with C below
 one wave's span, and one shape per LN register tile (NV = 1, 2, 4)."""
@@ -347,6 +348,88 @@ def test_determinism_and_generator_use(shared_dim):
     assert torch.equal(m1, m3)
     assert not torch.equal(m1, m2), "consecutive calls drew one mask"
     assert not torch.equal(m1, m4), "the seed does not reach the mask"
+
+
+# ---------------------------------------------------------------------------
+# the two mask maps share one keying
+# ---------------------------------------------------------------------------
+
+# shared extent 1: the shared map is the identity, as the flat map is; the
+# last two reach the LN register tiles NV = 2 and NV = 4
+UNIT_EXTENT = [((2, 1, 7, 24), 1), ((2, 5, 1, 24), 2), ((1, 1, 4, 520), 1),
+               ((1, 1, 3, 1032), 1)]
+
+
+def _generator_offset():
+    return torch.cuda.default_generators[torch.cuda.current_device()] \
+        .get_offset()
+
+
+def _scale_add_close(flat, shared, x, res, bias, dtype, what):
+    """The flat kernels may contract the scale into the add, the shared ones
+    round the product on its own: two roundings of at most 2**-24 each,
+    relative to terms no larger than |res| + |x + b| * pinv, hence
+    |flat - shared| <= 2**-23 * (|res| + |x + b| * pinv) in fp32; the
+    2-byte dtypes add one rounding of the output on top."""
+    xb = x.float() + bias.float() if bias is not None else x.float()
+    pinv = 1.0 / (1.0 - P)
+    bound = 2.0 ** -23 * (res.float().abs() + xb.abs() * pinv) \
+        + ONE_ROUNDING[dtype] * shared.float().abs()
+    err = (flat.float() - shared.float()).abs()
+    print(f"{what}: max err {err.max().item():.3e}, "
+          f"max (err - bound) {(err - bound).max().item():.3e}, "
+          f"{(err > 0).sum().item()} of {err.numel()} differ")
+    assert (err <= bound).all(), what
+
+
+@pytest.mark.parametrize("with_bias", [False, True])
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("shape,shared_dim", UNIT_EXTENT)
+def test_unit_shared_extent_is_the_flat_map(shape, shared_dim, dtype,
+                                            with_bias):
+    """With a shared extent of 1 the shared entries draw the mask of the
+    unshared entries from the same seed and reserve the same generator
+    range; backward, which has no add to contract, agrees bitwise. (normed
+    is a function of summed and is held to its own reference in
+    test_dropout_add_ln_forward_values.)"""
+    from unicore_amd import ops
+
+    C = shape[-1]
+    x, res, bias = _inputs(shape, dtype, with_bias, seed=13)
+    g = torch.Generator(device="cuda").manual_seed(14)
+    gamma = (torch.rand(C, device="cuda", generator=g) + 0.5).to(dtype)
+    beta = (torch.rand(C, device="cuda", generator=g) - 0.5).to(dtype)
+
+    torch.manual_seed(27)
+    out_f, mask_f = ops.dropout_add_fwd(x, res, P, True, bias)
+    off_f = _generator_offset()
+    torch.manual_seed(27)
+    out_s, mask_s = ops.shared_dropout_add_fwd(x, res, P, shared_dim, bias)
+    off_s = _generator_offset()
+    assert torch.equal(mask_f, mask_s), "add: masks differ"
+    assert off_f == off_s, (off_f, off_s)
+    _scale_add_close(out_f, out_s, x, res, bias, dtype, f"out {shape} {dtype}")
+
+    torch.manual_seed(28)
+    _, sum_f, lmask_f, _, _ = ops.dropout_add_ln_fwd(
+        x, res, bias, gamma, beta, P, True, 1e-5)
+    off_f = _generator_offset()
+    torch.manual_seed(28)
+    _, sum_s, lmask_s, _, _ = ops.shared_dropout_add_ln_fwd(
+        x, res, bias, gamma, beta, P, shared_dim, 1e-5)
+    off_s = _generator_offset()
+    assert torch.equal(lmask_f, lmask_s), "ln: masks differ"
+    assert off_f == off_s, (off_f, off_s)
+    _scale_add_close(sum_f, sum_s, x, res, bias, dtype,
+                     f"summed {shape} {dtype}")
+
+    grad = _inputs(shape, dtype, False, seed=15)[0]
+    bias_dim = C if with_bias else 0
+    dx_f, db_f = ops.dropout_add_bwd(grad, mask_f, P, bias_dim)
+    dx_s, db_s = ops.shared_dropout_add_bwd(grad, mask_f, P, shared_dim,
+                                            bias_dim)
+    assert torch.equal(dx_f, dx_s), "dx differs"
+    assert db_f.shape == db_s.shape and torch.equal(db_f, db_s), "dbias differs"
 
 
 # ---------------------------------------------------------------------------

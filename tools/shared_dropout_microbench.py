@@ -7,7 +7,7 @@ forward alone and forward+backward. Three columns per line:
 
   eager   UNICORE_SHARED_DROPOUT_FUSED=0: eager mask multiply, then the
           fused join at p = 0
-  fused   UNICORE_SHARED_DROPOUT_FUSED=1: csrc/shared_dropout.hip
+  fused   UNICORE_SHARED_DROPOUT_FUSED=1: the join kernels, shared mask map
   unshared  the existing join at the same p (no shared_dim): the bandwidth
           yardstick, an activation-sized draw and mask
 

@@ -16,21 +16,34 @@ import os
 import torch
 import torch.nn.functional as F
 
+from unicore_amd.modules.dropout_add import save_join, unmap_grad
 
-class _DropoutAddLN(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, res, bias, gamma, beta, p, is_training, eps):
-        from unicore_amd import ops
 
+def _ln_fwd(ctx, x, res, bias, gamma, beta, p, is_training, eps, shared_dim):
+    """Forward of both autograd functions: (normed, summed)."""
+    from unicore_amd import ops
+
+    if shared_dim is None:
         normed, summed, dmask, mean, invvar = ops.dropout_add_ln_fwd(
             x.contiguous(), res.contiguous(), bias, gamma.contiguous(),
             beta.contiguous(), p, is_training, eps,
         )
-        ctx.save_for_backward(summed, dmask, mean, invvar, gamma)
-        ctx.p = p
-        ctx.bias_dim = bias.numel() if bias is not None else 0
-        ctx.bias_dtype = bias.dtype if bias is not None else None
-        return normed
+    else:
+        normed, summed, dmask, mean, invvar = ops.shared_dropout_add_ln_fwd(
+            x.contiguous(), res.contiguous(), bias, gamma.contiguous(),
+            beta.contiguous(), p, shared_dim, eps,
+        )
+    ctx.save_for_backward(summed, dmask, mean, invvar, gamma)
+    save_join(ctx, p, bias, shared_dim)
+    return normed, summed
+
+
+class _DropoutAddLN(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, res, bias, gamma, beta, p, is_training, eps,
+                shared_dim=None):
+        return _ln_fwd(ctx, x, res, bias, gamma, beta, p, is_training, eps,
+                       shared_dim)[0]
 
     @staticmethod
     def backward(ctx, d_norm):
@@ -40,14 +53,8 @@ class _DropoutAddLN(torch.autograd.Function):
         ds, dgamma, dbeta = ops.layernorm_bwd(
             d_norm.contiguous(), summed, mean, invvar, gamma
         )
-        dbias = None
-        if dmask.numel() == 0 and ctx.bias_dim == 0:
-            dx = ds
-        else:
-            dx, db = ops.dropout_add_bwd(ds, dmask, ctx.p, ctx.bias_dim)
-            if ctx.bias_dim:
-                dbias = db.to(ctx.bias_dtype)
-        return dx, ds, dbias, dgamma, dbeta, None, None, None
+        dx, dbias = unmap_grad(ctx, ds, dmask)
+        return dx, ds, dbias, dgamma, dbeta, None, None, None, None
 
 
 class _DropoutAddLNPre(torch.autograd.Function):
@@ -57,17 +64,10 @@ class _DropoutAddLNPre(torch.autograd.Function):
     dropout/bias unmap."""
 
     @staticmethod
-    def forward(ctx, x, res, bias, gamma, beta, p, is_training, eps):
-        from unicore_amd import ops
-
-        normed, summed, dmask, mean, invvar = ops.dropout_add_ln_fwd(
-            x.contiguous(), res.contiguous(), bias, gamma.contiguous(),
-            beta.contiguous(), p, is_training, eps,
-        )
-        ctx.save_for_backward(summed, dmask, mean, invvar, gamma)
-        ctx.p = p
-        ctx.bias_dim = bias.numel() if bias is not None else 0
-        ctx.bias_dtype = bias.dtype if bias is not None else None
+    def forward(ctx, x, res, bias, gamma, beta, p, is_training, eps,
+                shared_dim=None):
+        normed, summed = _ln_fwd(ctx, x, res, bias, gamma, beta, p,
+                                 is_training, eps, shared_dim)
         return summed, normed
 
     @staticmethod
@@ -86,14 +86,8 @@ class _DropoutAddLNPre(torch.autograd.Function):
             )
         if d_sum is not None:
             ds = ds + d_sum
-        dbias = None
-        if dmask.numel() == 0 and ctx.bias_dim == 0:
-            dx = ds
-        else:
-            dx, db = ops.dropout_add_bwd(ds, dmask, ctx.p, ctx.bias_dim)
-            if ctx.bias_dim:
-                dbias = db.to(ctx.bias_dtype)
-        return dx, ds, dbias, dgamma, dbeta, None, None, None
+        dx, dbias = unmap_grad(ctx, ds.contiguous(), dmask)
+        return dx, ds, dbias, dgamma, dbeta, None, None, None, None
 
 
 def _fuse_ok(x, residual, bias):
@@ -124,8 +118,8 @@ def _shared(x, residual, bias, p, is_training, shared_dim, fn, ln):
         return None, x, p, bias
     if (_fuse_ok(x, residual, bias) and sd.fuse_ok(x, residual, bias)
             and ln.weight.dtype == x.dtype and ln.bias.dtype == x.dtype):
-        return fn.apply(x, residual, bias, ln.weight, ln.bias, p, shared_dim,
-                        ln.eps), x, p, bias
+        return fn.apply(x, residual, bias, ln.weight, ln.bias, p, True,
+                        ln.eps, shared_dim), x, p, bias
     return None, sd.apply_shared_mask(x, p, shared_dim, bias), 0.0, None
 
 
@@ -138,10 +132,8 @@ def dropout_add_ln_pre(x, residual, ln, p, is_training, bias=None,
     ``shared_dim`` (1 or 2, 4-D input): one keep-mask per slice, broadcast
     along that axis (modules/shared_dropout.py)."""
     if shared_dim is not None:
-        from unicore_amd.modules.shared_dropout import _SharedDropoutAddLNPre
-
         out, x, p, bias = _shared(x, residual, bias, p, is_training,
-                                  shared_dim, _SharedDropoutAddLNPre, ln)
+                                  shared_dim, _DropoutAddLNPre, ln)
         if out is not None:
             return out
     if _fuse_ok(x, residual, bias):
@@ -164,10 +156,8 @@ def dropout_add_ln(x, residual, ln, p, is_training, bias=None,
     ``shared_dim`` as in ``dropout_add_ln_pre``.
     """
     if shared_dim is not None:
-        from unicore_amd.modules.shared_dropout import _SharedDropoutAddLN
-
         out, x, p, bias = _shared(x, residual, bias, p, is_training,
-                                  shared_dim, _SharedDropoutAddLN, ln)
+                                  shared_dim, _DropoutAddLN, ln)
         if out is not None:
             return out
     if _fuse_ok(x, residual, bias):

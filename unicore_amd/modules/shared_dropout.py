@@ -2,11 +2,13 @@
 DropoutRowwise / DropoutColumnwise): one keep-mask per slice of a
 ``(B, R, T, C)`` tensor, broadcast along ``shared_dim`` (1 or 2).
 
-``dropout_add``, ``dropout_add_ln_pre`` and ``dropout_add_ln`` route here
-when their ``shared_dim`` keyword is set and dropout is active. The fused
-path (csrc/shared_dropout.hip) draws the mask in-kernel and stores only the
-small bitfield, ``B*T*C/8`` or ``B*R*C/8`` bytes, which backward reads back
-through the same index map. The eager fallback multiplies by a broadcast
+``dropout_add``, ``dropout_add_ln_pre`` and ``dropout_add_ln`` consult the
+gates here when their ``shared_dim`` keyword is set and dropout is active.
+The fused path (the join kernels with the shared mask map,
+csrc/dropout_mask.h) draws the mask in-kernel and stores only the small
+bitfield, ``B*T*C/8`` or ``B*R*C/8`` bytes, which backward reads back
+through the same index map; the joins' own autograd functions carry
+``shared_dim``. The eager fallback multiplies by a broadcast
 ``F.dropout(ones(mask_shape))`` and hands the product to the p = 0 join.
 """
 
@@ -58,105 +60,3 @@ def apply_shared_mask(x, p, shared_dim, bias=None):
     if bias is not None:
         x = x + bias
     return x * keep
-
-
-class _SharedDropoutAdd(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, res, bias, p, shared_dim):
-        from unicore_amd import ops
-
-        out, dmask = ops.shared_dropout_add_fwd(
-            x.contiguous(), res.contiguous(), p, shared_dim, bias
-        )
-        ctx.p = p
-        ctx.shared_dim = shared_dim
-        ctx.bias_dim = bias.numel() if bias is not None else 0
-        ctx.bias_dtype = bias.dtype if bias is not None else None
-        ctx.save_for_backward(dmask)
-        return out
-
-    @staticmethod
-    def backward(ctx, grad):
-        from unicore_amd import ops
-
-        (dmask,) = ctx.saved_tensors
-        grad = grad.contiguous()
-        dx, db = ops.shared_dropout_add_bwd(
-            grad, dmask, ctx.p, ctx.shared_dim, ctx.bias_dim
-        )
-        dbias = db.to(ctx.bias_dtype) if ctx.bias_dim else None
-        return dx, grad, dbias, None, None
-
-
-class _SharedDropoutAddLN(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, res, bias, gamma, beta, p, shared_dim, eps):
-        from unicore_amd import ops
-
-        normed, summed, dmask, mean, invvar = ops.shared_dropout_add_ln_fwd(
-            x.contiguous(), res.contiguous(), bias, gamma.contiguous(),
-            beta.contiguous(), p, shared_dim, eps,
-        )
-        ctx.save_for_backward(summed, dmask, mean, invvar, gamma)
-        ctx.p = p
-        ctx.shared_dim = shared_dim
-        ctx.bias_dim = bias.numel() if bias is not None else 0
-        ctx.bias_dtype = bias.dtype if bias is not None else None
-        return normed
-
-    @staticmethod
-    def backward(ctx, d_norm):
-        from unicore_amd import ops
-
-        summed, dmask, mean, invvar, gamma = ctx.saved_tensors
-        ds, dgamma, dbeta = ops.layernorm_bwd(
-            d_norm.contiguous(), summed, mean, invvar, gamma
-        )
-        dx, db = ops.shared_dropout_add_bwd(
-            ds, dmask, ctx.p, ctx.shared_dim, ctx.bias_dim
-        )
-        dbias = db.to(ctx.bias_dtype) if ctx.bias_dim else None
-        return dx, ds, dbias, dgamma, dbeta, None, None, None
-
-
-class _SharedDropoutAddLNPre(torch.autograd.Function):
-    """Pre-LN chain variant (see _DropoutAddLNPre): returns the summed
-    stream and the normed view, backward joins both gradients before the
-    mask unmap."""
-
-    @staticmethod
-    def forward(ctx, x, res, bias, gamma, beta, p, shared_dim, eps):
-        from unicore_amd import ops
-
-        normed, summed, dmask, mean, invvar = ops.shared_dropout_add_ln_fwd(
-            x.contiguous(), res.contiguous(), bias, gamma.contiguous(),
-            beta.contiguous(), p, shared_dim, eps,
-        )
-        ctx.save_for_backward(summed, dmask, mean, invvar, gamma)
-        ctx.p = p
-        ctx.shared_dim = shared_dim
-        ctx.bias_dim = bias.numel() if bias is not None else 0
-        ctx.bias_dtype = bias.dtype if bias is not None else None
-        return summed, normed
-
-    @staticmethod
-    def backward(ctx, d_sum, d_norm):
-        from unicore_amd import ops
-
-        summed, dmask, mean, invvar, gamma = ctx.saved_tensors
-        if d_norm is None:
-            # normed output unused downstream: only the stream grad flows
-            ds = torch.zeros_like(summed)
-            dgamma = torch.zeros_like(gamma)
-            dbeta = torch.zeros_like(gamma)
-        else:
-            ds, dgamma, dbeta = ops.layernorm_bwd(
-                d_norm.contiguous(), summed, mean, invvar, gamma
-            )
-        if d_sum is not None:
-            ds = ds + d_sum
-        dx, db = ops.shared_dropout_add_bwd(
-            ds.contiguous(), dmask, ctx.p, ctx.shared_dim, ctx.bias_dim
-        )
-        dbias = db.to(ctx.bias_dtype) if ctx.bias_dim else None
-        return dx, ds, dbias, dgamma, dbeta, None, None, None

@@ -225,7 +225,7 @@ def shared_dropout_add_bwd(grad, dmask, p, shared_dim, bias_dim=0):
 
 
 def shared_dropout_supported(shape, dtype) -> bool:
-    # mirrors the host checks in csrc/shared_dropout.hip (the LN entry also
+    # mirrors the host checks in csrc/dropout_mask.h (the LN entry also
     # needs C <= 2048); pure Python so a missing extension still fails
     # loudly in the wrappers above
     import torch
