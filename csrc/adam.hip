@@ -38,8 +38,9 @@ __global__ void adam_kernel(T* __restrict__ p, float* __restrict__ m,
   }
 }
 
-// vectorized variant when n % 4 == 0 (16 B/lane for fp32, 8 B for 16-bit p/g
-// plus 16 B fp32 moments)
+// vectorized variant when n % 4 == 0 and every pointer is aligned for its
+// own vector (16 B/lane for fp32, 8 B for 16-bit p/g plus 16 B fp32 moments);
+// the host entry checks both
 template <typename T>
 __global__ void adam_kernel_vec(T* __restrict__ p, float* __restrict__ m,
                                 float* __restrict__ v, const T* __restrict__ g,
@@ -96,6 +97,10 @@ __global__ void adam_kernel_vec(T* __restrict__ p, float* __restrict__ m,
   }
 }
 
+bool aligned_to(const void* p, size_t bytes) {
+  return reinterpret_cast<uintptr_t>(p) % bytes == 0;
+}
+
 }  // namespace
 
 void fused_adam(at::Tensor p, at::Tensor m, at::Tensor v, at::Tensor g, double lr,
@@ -123,10 +128,18 @@ void fused_adam(at::Tensor p, at::Tensor m, at::Tensor v, at::Tensor g, double l
   auto stream = at::cuda::getCurrentCUDAStream();
   const int64_t n4 = n / 4;
   const int grid = unicore_grid((n4 + 255) / 256);
+  // A vector access at an address that is not a multiple of its width is
+  // undefined; views into a flat buffer (flat_ddp gradients) start at any
+  // element. Those, like n % 4 != 0, take the scalar kernel.
+  const size_t pg_vec = 4 * (size_t)p.element_size();
+  const bool vec = n % 4 == 0 && aligned_to(m.data_ptr(), 16) &&
+                   aligned_to(v.data_ptr(), 16) &&
+                   aligned_to(p.data_ptr(), pg_vec) &&
+                   aligned_to(g.data_ptr(), pg_vec);
 
   switch (p.scalar_type()) {
     case at::ScalarType::Float: {
-      if (n % 4 == 0)
+      if (vec)
         adam_kernel_vec<float><<<grid, 256, 0, stream>>>(
             p.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
             g.data_ptr<float>(), n4, (float)step_size, (float)beta1, (float)beta2,
@@ -141,7 +154,7 @@ void fused_adam(at::Tensor p, at::Tensor m, at::Tensor v, at::Tensor g, double l
     case at::ScalarType::Half: {
       auto* pp = reinterpret_cast<__half*>(p.data_ptr());
       auto* gp = reinterpret_cast<const __half*>(g.data_ptr());
-      if (n % 4 == 0)
+      if (vec)
         adam_kernel_vec<__half><<<grid, 256, 0, stream>>>(
             pp, m.data_ptr<float>(), v.data_ptr<float>(), gp, n4, (float)step_size,
             (float)beta1, (float)beta2, (float)eps, inv_scale, wd_factor);
@@ -154,7 +167,7 @@ void fused_adam(at::Tensor p, at::Tensor m, at::Tensor v, at::Tensor g, double l
     case at::ScalarType::BFloat16: {
       auto* pp = reinterpret_cast<__hip_bfloat16*>(p.data_ptr());
       auto* gp = reinterpret_cast<const __hip_bfloat16*>(g.data_ptr());
-      if (n % 4 == 0)
+      if (vec)
         adam_kernel_vec<__hip_bfloat16><<<grid, 256, 0, stream>>>(
             pp, m.data_ptr<float>(), v.data_ptr<float>(), gp, n4, (float)step_size,
             (float)beta1, (float)beta2, (float)eps, inv_scale, wd_factor);

@@ -35,8 +35,23 @@ __global__ void l2norm_chunk_kernel(TensorListMeta meta, int chunk_size,
     const T* p = reinterpret_cast<const T*>(meta.ptrs[t]);
     const int64_t base = (c - meta.chunk_start[t]) * (int64_t)chunk_size;
     const int64_t end = min(base + (int64_t)chunk_size, meta.numels[t]);
-    // vectorized main body: 4 elems/lane
-    int64_t i = base + (int64_t)threadIdx.x * 4;
+    // Elements in front of the first one that is aligned for the 4-element
+    // vector: 0 for an allocation, 1..3 for a view into a flat buffer.
+    // chunk_size % 4 == 0, so it is the same in every chunk of the tensor,
+    // and it depends on the pointer alone: the branch is block-uniform.
+    constexpr uintptr_t kVecBytes = 4 * sizeof(T);
+    const int head =
+        (int)((kVecBytes - reinterpret_cast<uintptr_t>(p) % kVecBytes) %
+              kVecBytes / sizeof(T));
+    if (head != 0) {
+      const int64_t ih = base + threadIdx.x;
+      if ((int)threadIdx.x < head && ih < end) {
+        const float f = Cvt<T>::to_f(p[ih]);
+        acc += f * f;
+      }
+    }
+    // vectorized main body: 4 elems/lane, from the first aligned element
+    int64_t i = base + head + (int64_t)threadIdx.x * 4;
     for (; i + 3 < end; i += 256 * 4) {
       float f[4];
       if constexpr (sizeof(T) == 2) {
@@ -54,7 +69,8 @@ __global__ void l2norm_chunk_kernel(TensorListMeta meta, int chunk_size,
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc += f[j] * f[j];
     }
-    // tail (only the last chunk of a tensor can be ragged)
+    // tail (the last chunk of a tensor can be ragged, and a chunk with a
+    // head ends 4 - head elements past its last whole vector)
     for (; i < end; ++i) {
       const float f = Cvt<T>::to_f(p[i]);
       acc += f * f;
@@ -91,6 +107,10 @@ __global__ void sqrt_inplace_kernel(float* x) { x[0] = sqrtf(x[0]); }
 // Returns sqrt(sum over all tensors of sum(x^2)) as a 0-dim fp32 CUDA tensor.
 at::Tensor multi_tensor_l2norm(int64_t chunk_size, std::vector<at::Tensor> tensors) {
   TORCH_CHECK(!tensors.empty(), "multi_tensor_l2norm: empty tensor list");
+  // chunks of one tensor must start at the same offset from a vector boundary
+  TORCH_CHECK(chunk_size > 0 && chunk_size % 4 == 0,
+              "multi_tensor_l2norm: chunk_size must be a positive multiple of 4, got ",
+              chunk_size);
   const auto st = tensors[0].scalar_type();
   for (auto& t : tensors) {
     TORCH_CHECK(t.is_cuda() && t.is_contiguous(),

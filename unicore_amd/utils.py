@@ -422,13 +422,12 @@ def fp32_to_bf16_sr(t_fp32: torch.Tensor, t_bf16: torch.Tensor):
         0, 1 << 16, t_fp32.shape, dtype=torch.int32, device=t_fp32.device
     )
     dithered = bits + rand
-    # truncate low 16 bits -> bf16 pattern
-    truncated = dithered & ~0xFFFF
     # Handle inf/nan: keep original value (bit-dither can overflow exponent)
-    out = truncated.view(torch.float32)
     bad = ~torch.isfinite(t_fp32)
-    out = torch.where(bad, t_fp32, out)
-    t_bf16.copy_(out.bfloat16())
+    out = torch.where(bad, bits, dithered)
+    # truncate low 16 bits -> bf16 pattern. Moved as bits, like the kernel:
+    # a float -> bf16 cast may rewrite a NaN's payload and sign.
+    t_bf16.copy_((out >> 16).to(torch.int16).view(torch.bfloat16))
 
 
 @contextlib.contextmanager
