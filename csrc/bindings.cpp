@@ -131,6 +131,15 @@ std::vector<at::Tensor> shared_dropout_add_backward(at::Tensor grad,
                                                     at::Tensor dmask, double p,
                                                     int64_t shared_dim,
                                                     int64_t bias_dim);
+at::Tensor pair_coord_forward(at::Tensor pair, at::Tensor pair0,
+                              at::Tensor coords, at::Tensor inv_n,
+                              std::optional<at::Tensor> pad, at::Tensor W1,
+                              at::Tensor b1, at::Tensor W2, at::Tensor b2);
+std::vector<at::Tensor> pair_coord_backward(
+    at::Tensor grad, at::Tensor pair, at::Tensor pair0, at::Tensor coords,
+    at::Tensor inv_n, std::optional<at::Tensor> pad, at::Tensor W1,
+    at::Tensor b1, at::Tensor W2, at::Tensor b2);
+bool pair_coord_supported(int64_t H);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("softmax_dropout_forward", &softmax_dropout_forward,
@@ -231,4 +240,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "shared-axis dropout + residual + LayerNorm -> (normed, summed, mask, mean, invvar)");
   m.def("shared_dropout_add_backward", &shared_dropout_add_backward,
         "shared-axis dropout backward through the small mask -> (dx, dbias)");
+  m.def("pair_coord_forward", &pair_coord_forward,
+        "equivariant coordinate head: (B,H,L,L) pair track -> (B,L,3) update");
+  m.def("pair_coord_backward", &pair_coord_backward,
+        "coordinate head backward -> (dpair, dW1, db1, dW2, db2)");
+  m.def("pair_coord_supported", &pair_coord_supported,
+        "coordinate head kernel supports this head count");
 }

@@ -1,6 +1,10 @@
 #!/usr/bin/env bash
 # Uni-Mol-style 3D molecular pretraining (pair-bias attention + RMSNorm +
 # coordinate denoising) on N MI355X GPUs — BASELINE.json stress config 4.
+#
+# Pair track + SE(3)-equivariant coordinate head (Uni-Mol's own head): pass
+# the flag after the GPU count,
+#   bash train_unimol_test.sh 8 --coord-head equivariant
 set -e
 n_gpu=${1:-8}
 exec python -m torch.distributed.run --nnodes=1 --nproc-per-node "$n_gpu" \

@@ -39,6 +39,7 @@ HIP_SOURCES = [
     "csrc/triangle.hip",
     "csrc/outer_product.hip",
     "csrc/tri_attn.hip",
+    "csrc/pair_coord.hip",
 ]
 
 setup(

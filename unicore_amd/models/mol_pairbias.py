@@ -24,6 +24,7 @@ from unicore_amd.models import (
     register_model_architecture,
 )
 from unicore_amd.modules import (
+    PairCoordHead,
     RMSNorm,
     SelfMultiheadAttention,
     dropout_add,
@@ -103,7 +104,9 @@ class PairBiasEncoderLayer(nn.Module):
         self.dropout = dropout
         self.activation_dropout = activation_dropout
 
-    def forward(self, x, bias, padding_mask):
+    def forward(self, x, bias, padding_mask, return_pair=False):
+        """``return_pair``: also return the pre-softmax attention logits
+        (B, H, L, L), the pair track's next state."""
         # same fused-op + bias-folding structure as TransformerEncoderLayer
         fold = False
         if x.is_cuda and os.environ.get("UNICORE_FOLD_BIAS", "1") == "1":
@@ -120,7 +123,12 @@ class PairBiasEncoderLayer(nn.Module):
             )
         residual = x
         x = self.attn_norm(x)
-        x = self.attn(x, attn_bias=bias, skip_out_bias=fold)
+        attn_weights = None
+        if return_pair:
+            x, attn_weights, _ = self.attn(x, attn_bias=bias, return_attn=True,
+                                           skip_out_bias=fold)
+        else:
+            x = self.attn(x, attn_bias=bias, skip_out_bias=fold)
         x = dropout_add(
             x, residual, self.dropout, self.training,
             bias=self.attn.out_proj.bias if fold else None,
@@ -138,6 +146,8 @@ class PairBiasEncoderLayer(nn.Module):
             x = gelu_dropout(self.fc1(x), self.activation_dropout, self.training)
             x = self.fc2(x)
             x = dropout_add(x, residual, self.dropout, self.training)
+        if return_pair:
+            return x, attn_weights
         return x
 
 
@@ -154,6 +164,12 @@ class MolPairBiasModel(BaseUnicoreModel):
         parser.add_argument("--attention-dropout", type=float)
         parser.add_argument("--activation-dropout", type=float)
         parser.add_argument("--max-seq-len", type=int)
+        parser.add_argument(
+            "--coord-head", choices=["linear", "equivariant"],
+            help="linear: nn.Linear(E, 3) on the atom track; equivariant: "
+            "carry the attention logits through the layers as a pair track "
+            "and read the coordinate update off it (PairCoordHead)",
+        )
 
     def __init__(self, args, dictionary):
         super().__init__()
@@ -182,7 +198,11 @@ class MolPairBiasModel(BaseUnicoreModel):
         self.lm_head = nn.Linear(E, len(dictionary), bias=False)
         self.lm_head.weight = self.embed_tokens.weight  # tied
         # per-atom 3D coordinate delta head (SE(3)-style denoising target)
-        self.coord_head = nn.Linear(E, 3)
+        self.equivariant = args.coord_head == "equivariant"
+        if self.equivariant:
+            self.coord_head = PairCoordHead(args.encoder_attention_heads)
+        else:
+            self.coord_head = nn.Linear(E, 3)
         self.apply(init_bert_params)
 
     @classmethod
@@ -193,12 +213,23 @@ class MolPairBiasModel(BaseUnicoreModel):
         padding_mask = src_tokens.eq(self.padding_idx)
         x = self.embed_tokens(src_tokens)
         bias = self.pair_bias(src_coord, padding_mask)
-        for layer in self.layers:
-            x = layer(x, bias, padding_mask)
+        if self.equivariant:
+            # pair track: each layer's attention logits are the next layer's
+            # bias; the head reads the update off last logits - first bias
+            pair = bias
+            for layer in self.layers:
+                x, pair = layer(x, pair, padding_mask, return_pair=True)
+            coord_delta = self.coord_head(
+                pair.contiguous(), bias, src_coord, padding_mask
+            )
+        else:
+            for layer in self.layers:
+                x = layer(x, bias, padding_mask)
         x = self.final_norm(x)
         logits = self.lm_head(x)
-        coord_delta = self.coord_head(x).float()
-        return logits, coord_delta
+        if not self.equivariant:
+            coord_delta = self.coord_head(x)
+        return logits, coord_delta.float()
 
 
 @register_model_architecture("mol_pairbias", "mol_pairbias")
@@ -212,3 +243,4 @@ def base_mol_architecture(args):
     args.attention_dropout = getattr(args, "attention_dropout", 0.1)
     args.activation_dropout = getattr(args, "activation_dropout", 0.0)
     args.max_seq_len = getattr(args, "max_seq_len", 512)
+    args.coord_head = getattr(args, "coord_head", "linear")

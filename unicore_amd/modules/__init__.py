@@ -6,6 +6,7 @@ from .softmax_dropout import softmax_dropout
 from .gelu_dropout import gelu_dropout
 from .dropout_add import dropout_add
 from .gaussian import gaussian_basis
+from .pair_coord import PairCoordHead, pair_coord
 from .gated_mul import gated_mul
 from .triangle import triangle_multiply
 from .outer_product import outer_product_mean

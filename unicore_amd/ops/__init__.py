@@ -304,6 +304,35 @@ def gaussian_pair_bias_supported(n_kernels, n_heads) -> bool:
     )
 
 
+def pair_coord_fwd(pair, pair0, coords, inv_n, pad, w1, b1, w2, b2):
+    """Equivariant coordinate head: pair/pair0 (B,H,L,L) contiguous, coords
+    (B,L,3) fp32, inv_n (B,) fp32, pad (B,L) bool or None, fp32 fc1/fc2
+    parameters -> (B,L,3) fp32 update. csrc/pair_coord.hip."""
+    require_kernels()
+    return _kernels.pair_coord_forward(
+        pair, pair0, coords, inv_n, pad, w1, b1, w2, b2
+    )
+
+
+def pair_coord_bwd(grad, pair, pair0, coords, inv_n, pad, w1, b1, w2, b2):
+    """-> (dpair in the dtype of pair, dW1 (H,H), db1 (H), dW2 (H), db2 (1)),
+    the weight gradients fp32 and deterministic."""
+    require_kernels()
+    return _kernels.pair_coord_backward(
+        grad, pair, pair0, coords, inv_n, pad, w1, b1, w2, b2
+    )
+
+
+def pair_coord_supported(H, dtype) -> bool:
+    # mirrors the host check in csrc/pair_coord.hip; pure Python so a missing
+    # extension still fails loudly in pair_coord_fwd
+    import torch
+
+    return int(H) in (8, 16) and dtype in (
+        torch.float32, torch.float16, torch.bfloat16
+    )
+
+
 def softmax_dropout_bwd_bias(grad, softmax_out, dmask, p, bb, bq, od):
     """In-place softmax backward that also returns the broadcast bias grad
     (fp32, (bb*bq, k)) without re-reading the grad tensor."""
