@@ -15,17 +15,21 @@
 //   C (16x16): lane l -> col l&15,  rows (l>>4)*4+[0..4)
 // P is redistributed C-layout -> A-layout through a per-wave LDS tile.
 // Dropout keep bits are a pure function of (seed, bh*L+q, kv):
-//   philox(seed, bh*L+q, kv/4) component kv%4 — recomputable by the
-// backward kernels with no stored mask.
+//   16-bit field kv%8 of philox(seed, bh*L+q, kv/8), kept when it is
+//   >= p * 65536 (common.h keep16x8) — recomputable by the backward
+// kernels with no stored mask.
 //
 // Per-row LSE (= m + log l) is saved for the backward recomputation.
+//
+// Every kernel below is assembled from the device blocks that follow; a
+// block is the only place its step is written.  docs/KERNELS.md ("Flash
+// attention") lists which kernel runs when and what each block owns.
 #include "common.h"
-
-#include <torch/extension.h>
-#include <ATen/cuda/CUDAContext.h>
-#include <ATen/cuda/CUDAGeneratorImpl.h>
+#include "dispatch.h"
 
 #include <optional>
+#include <tuple>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -36,6 +40,8 @@ typedef __attribute__((__vector_size__(4 * sizeof(float)))) float f32x4;
 constexpr int BM = 64;   // query rows per block
 constexpr int BN = 64;   // kv rows per tile
 constexpr int HD = 64;   // head dim
+// longest L whose whole V^T / K^T the resident kernels keep in LDS (64 KB)
+constexpr int LRES = 512;
 
 __device__ __forceinline__ bf16x8 load_frag(const uint16_t* p) {
   union {
@@ -44,6 +50,14 @@ __device__ __forceinline__ bf16x8 load_frag(const uint16_t* p) {
   } U;
   U.u = *reinterpret_cast<const uint4*>(p);
   return U.v;
+}
+
+__device__ __forceinline__ f32x4 mfma(bf16x8 a, bf16x8 b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
+
+__device__ __forceinline__ float bf16_at(const uint16_t* p, int i) {
+  return __bfloat162float(reinterpret_cast<const __hip_bfloat16*>(p)[i]);
 }
 
 // reduce a per-lane value across the 16 lanes that share a C-tile row
@@ -59,8 +73,199 @@ __device__ __forceinline__ float rowgroup_sum(float v) {
   return v;
 }
 
-// keep-decision for dropout: element (row_global = bh*L + q, col kv) via
-// the shared 16-bit keep definition: keep16x8(seed, row_global, kv_block).
+// ---- the shared blocks -----------------------------------------------------
+
+// Where a lane sits: wave 0..3 of the block, fragment k-group / C row group
+// lg, fragment row (A) / col (B, C) lr, and the first of the rows_per_wave
+// rows (q rows in forward and dq, kv rows in dkv) that its wave owns.
+struct Lane {
+  int wid, lg, lr, row0;
+};
+
+__device__ __forceinline__ Lane lane_coords(int rows_per_wave) {
+  const int wid = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
+  return {wid, lane >> 4, lane & 15,
+          ((int)blockIdx.x * 4 + wid) * rows_per_wave};
+}
+
+// An additive bias or mask, contiguous bf16 (nb, q, L), broadcast over the
+// (BH, L, L) scores by the contract shared with softmax_dropout:
+//   source row of score row (bh, qrow) = ((bh / od) % nb) * q + (qrow % q)
+struct Src {
+  const uint16_t* ptr = nullptr;
+  int64_t nb = 1;
+  int q = 1;
+  int64_t od = 1;
+
+  __device__ __forceinline__ int64_t row_index(int64_t bh, int qrow) const {
+    return ((bh / od) % nb) * q + (qrow % q);
+  }
+  __device__ __forceinline__ const uint16_t* row(int64_t bh, int qrow,
+                                                 int L) const {
+    return ptr + row_index(bh, qrow) * (int64_t)L;
+  }
+};
+
+// dropout scalars; pinv = 1 / (1 - p), pthresh = keep16_threshold(p)
+struct Drop {
+  float pinv = 1.f;
+  uint32_t pthresh = 0;
+  uint64_t seed = 0;
+};
+
+// A transposed tile in LDS is [d][x] with x XOR-swizzled in 8-element blocks
+// keyed on d & 7, so the B-fragment reads (16 d rows, one x range) are
+// bank-conflict-free (guide T2 pattern).  Writer and readers go through swz.
+__device__ __forceinline__ int swz(int d, int x) { return x ^ ((d & 7) << 3); }
+
+// Stage 64 rows of a (rows, HD) tensor, the first at src, transposed into
+// dst[d][col0 + 0..63] (row pitch `pitch`): thread handles row tid/4,
+// d block (tid%4)*16.  The resident kernels call it once per tile of L, the
+// tiled ones once per iteration (ping-pong: dst = buffer tile & 1).
+__device__ __forceinline__ void stage_transposed(uint16_t* dst, int pitch,
+                                                 int col0,
+                                                 const uint16_t* src) {
+  const int x = col0 + ((int)threadIdx.x >> 2);
+  const int st_d0 = ((int)threadIdx.x & 3) * 16;
+  const __hip_bfloat16* row = reinterpret_cast<const __hip_bfloat16*>(src) +
+                              ((int)threadIdx.x >> 2) * HD + st_d0;
+  float f0[8], f1[8];
+  load8(row, f0);
+  load8(row + 8, f1);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int d0 = st_d0 + j;
+    const int d1 = st_d0 + 8 + j;
+    dst[d0 * pitch + swz(d0, x)] = f32_to_bf16_bits(f0[j]);
+    dst[d1 * pitch + swz(d1, x)] = f32_to_bf16_bits(f1[j]);
+  }
+}
+
+// acc[m] += A[m] * T for M A fragments (16 x 32, k = x .. x+31) against the
+// staged transpose T[d][x]: each 16 B B-fragment read feeds M MFMAs.
+template <int M>
+__device__ __forceinline__ void mma_staged(const bf16x8 (&a)[M],
+                                           const uint16_t* t, int pitch, int x,
+                                           const Lane& ln,
+                                           f32x4 (&acc)[M][4]) {
+#pragma unroll
+  for (int cb = 0; cb < 4; ++cb) {
+    const int d = cb * 16 + ln.lr;
+    const bf16x8 b = load_frag(t + d * pitch + swz(d, x + ln.lg * 8));
+#pragma unroll
+    for (int m = 0; m < M; ++m) acc[m][cb] = mfma(a[m], b, acc[m][cb]);
+  }
+}
+
+// A fragments of 16 rows (the first at global row `row`) of a (rows, HD)
+// tensor: lane holds row lr, d = ks*32 + lg*8 + [0..8)
+__device__ __forceinline__ void load_a(const uint16_t* base, int64_t row,
+                                       const Lane& ln, bf16x8 (&a)[2]) {
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks)
+    a[ks] = load_frag(base + (row + ln.lr) * HD + ks * 32 + ln.lg * 8);
+}
+
+// One k-step of a score tile: the B fragment of global row cb*16 + lr of the
+// 64 rows at `rows` (k = d = ks*32 + lg*8 + [0..8)) feeds the M MFMAs of M
+// 16-row A tiles.
+template <int M>
+__device__ __forceinline__ void score_step(const bf16x8 (&a)[M][2],
+                                           const uint16_t* rows, int cb, int ks,
+                                           const Lane& ln, f32x4 (&acc)[M]) {
+  const bf16x8 b = load_frag(rows + (cb * 16 + ln.lr) * (int64_t)HD + ks * 32 +
+                             ln.lg * 8);
+#pragma unroll
+  for (int m = 0; m < M; ++m) acc[m] = mfma(a[m][ks], b, acc[m]);
+}
+
+// s[m] = A[m] * rows^T: M 16-row A tiles against the same 64 global rows, as
+// four 16 x 16 C tiles each.
+template <int M>
+__device__ __forceinline__ void score_tile(const bf16x8 (&a)[M][2],
+                                           const uint16_t* rows,
+                                           const Lane& ln, f32x4 (&s)[M][4]) {
+#pragma unroll
+  for (int cb = 0; cb < 4; ++cb) {
+    f32x4 acc[M] = {};
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) score_step<M>(a, rows, cb, ks, ln, acc);
+#pragma unroll
+    for (int m = 0; m < M; ++m) s[m][cb] = acc[m];
+  }
+}
+
+// v + bias[kv] + mask[kv], added in that order.  The forward starts from
+// v = 0 and adds the sum to the score; the backward starts from the score.
+template <bool HAS_BIAS, bool HAS_MASK>
+__device__ __forceinline__ float add_bias_mask(float v, const uint16_t* bias_row,
+                                               const uint16_t* mask_row,
+                                               int kv) {
+  if (HAS_BIAS) v += bf16_at(bias_row, kv);
+  if (HAS_MASK) v += bf16_at(mask_row, kv);
+  return v;
+}
+
+__device__ __forceinline__ float p_from_lse(float s, float lse) {
+  return __expf(s - lse);
+}
+
+// bias rows of the 4 C rows q_first + [0..4) of a wave's tile
+template <bool HAS_BIAS>
+__device__ __forceinline__ void bias_rows4(const Src& bias, int64_t bh,
+                                           int q_first, int L,
+                                           const uint16_t* (&rows)[4]) {
+  if (HAS_BIAS) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) rows[r] = bias.row(bh, q_first + r, L);
+  }
+}
+
+// the mask is (nb, 1, L): one row per (bh / od) batch, shared by all q
+template <bool HAS_MASK>
+__device__ __forceinline__ const uint16_t* mask_row_of(const Src& mask,
+                                                       int64_t bh, int L) {
+  return HAS_MASK ? mask.row(bh, 0, L) : nullptr;
+}
+
+// P = exp(S + bias + mask - lse) on a 16 x 64 C-layout tile (dq kernels)
+template <bool HAS_BIAS, bool HAS_MASK>
+__device__ __forceinline__ void p_tile(f32x4 (&s)[4],
+                                       const uint16_t* const (&bias_rows)[4],
+                                       const uint16_t* mask_row,
+                                       const float (&lse_r)[4], int kv0,
+                                       const Lane& ln) {
+#pragma unroll
+  for (int cb = 0; cb < 4; ++cb) {
+    const int kv = kv0 + cb * 16 + ln.lr;
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      s[cb][r] = p_from_lse(
+          add_bias_mask<HAS_BIAS, HAS_MASK>(s[cb][r], bias_rows[r], mask_row, kv),
+          lse_r[r]);
+  }
+}
+
+// C layout -> A layout through a wave-private 16 x 64 LDS tile.  The
+// compiler's lgkmcnt waits order write -> read within the wave, and no other
+// wave touches the tile, so no barrier is needed.
+__device__ __forceinline__ void c_store(uint16_t (&t)[16][BN],
+                                        const f32x4 (&c)[4], const Lane& ln) {
+#pragma unroll
+  for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      t[ln.lg * 4 + r][cb * 16 + ln.lr] = f32_to_bf16_bits(c[cb][r]);
+}
+
+// A frag of the tile: row = lr, cols ks2*32 + lg*8 + [0..8)
+__device__ __forceinline__ bf16x8 a_load(const uint16_t (&t)[16][BN], int ks2,
+                                         const Lane& ln) {
+  return load_frag(&t[ln.lr][ks2 * 32 + ln.lg * 8]);
+}
+
+// keep bits of P[row, kv0 .. kv0+7]; all true without dropout
 template <bool DROP>
 __device__ __forceinline__ void keep_bits8(uint64_t seed, uint64_t subseq,
                                            int kv0, uint32_t pthresh,
@@ -73,57 +278,99 @@ __device__ __forceinline__ void keep_bits8(uint64_t seed, uint64_t subseq,
   keep16x8(seed, subseq, kv0, pthresh, keep);
 }
 
-// V^T-resident forward (L <= 512): whole V^T staged once, kv loop runs
-// barrier-free (same PMC-driven rationale as the dq K-resident variant).
-template <bool HAS_BIAS, bool HAS_MASK, bool DROP, int LMAX>
-__global__ __launch_bounds__(256) void flash_fwd_vres_kernel(
-    uint16_t* __restrict__ out, float* __restrict__ lse,
-    const uint16_t* __restrict__ qp, const uint16_t* __restrict__ kp,
-    const uint16_t* __restrict__ vp,
-    const uint16_t* __restrict__ bias, int64_t bias_nb, int bias_q, int64_t bias_od,
-    const uint16_t* __restrict__ mask, int64_t mask_nb, int mask_q, int64_t mask_od,
-    int L, float pinv, uint32_t pthresh, uint64_t seed) {
-  const int qt = blockIdx.x;
-  const int64_t bh = blockIdx.y;
-  const int wid = threadIdx.x >> 6;
-  const int lane = threadIdx.x & 63;
-  const int lg = lane >> 4;
-  const int lr = lane & 15;
-  const int q0 = qt * BM + wid * 16;
-  const int64_t qbase = (bh * L + q0) * HD;
-
-  __shared__ __attribute__((aligned(16))) uint16_t lds_p[4][16][BN];
-  __shared__ __attribute__((aligned(16))) uint16_t lds_vt[HD][LMAX];
-
-  {
-    const int st_kv0 = (int)threadIdx.x >> 2;
-    const int st_d0 = ((int)threadIdx.x & 3) * 16;
-    for (int c = 0; c < L / 64; ++c) {
-      const int kv = st_kv0 + c * 64;
-      float f0[8], f1[8];
-      load8(reinterpret_cast<const __hip_bfloat16*>(vp) +
-                (bh * L + kv) * (int64_t)HD + st_d0,
-            f0);
-      load8(reinterpret_cast<const __hip_bfloat16*>(vp) +
-                (bh * L + kv) * (int64_t)HD + st_d0 + 8,
-            f1);
+// dropout on the A fragment P[row, kv .. kv+7] (row = bh*L + q)
+template <bool DROP>
+__device__ __forceinline__ void drop_frag(bf16x8& ap, const Drop& dr,
+                                          int64_t row, int kv) {
+  if constexpr (DROP) {
+    bool keep[8];
+    keep16x8(dr.seed, (uint64_t)row, kv, dr.pthresh, keep);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int d0 = st_d0 + j;
-        const int d1 = st_d0 + 8 + j;
-        lds_vt[d0][kv ^ ((d0 & 7) << 3)] = f32_to_bf16_bits(f0[j]);
-        lds_vt[d1][kv ^ ((d1 & 7) << 3)] = f32_to_bf16_bits(f1[j]);
-      }
+    for (int j = 0; j < 8; ++j) {
+      float pv = bf16_bits_to_f32((uint16_t)(unsigned short)ap[j]);
+      pv = keep[j] ? pv * dr.pinv : 0.f;
+      ap[j] = (short)f32_to_bf16_bits(pv);
     }
   }
-  __syncthreads();
+}
 
-  bf16x8 aq[2];
+// dS = P o (keep * pinv * dP - Di) on the A fragments of row `row`, columns
+// kv .. kv+7; dsf is the fp32 value before rounding (atomic dbias path)
+template <bool DROP>
+__device__ __forceinline__ void ds_frag(const bf16x8& pa, const bf16x8& dpa,
+                                        float di_row, const Drop& dr,
+                                        int64_t row, int kv, bf16x8& dsa,
+                                        float (&dsf)[8]) {
+  bool keep[8];
+  if constexpr (DROP) keep16x8(dr.seed, (uint64_t)row, kv, dr.pthresh, keep);
 #pragma unroll
-  for (int ks = 0; ks < 2; ++ks)
-    aq[ks] = load_frag(qp + qbase + (int64_t)lr * HD + ks * 32 + lg * 8);
+  for (int j = 0; j < 8; ++j) {
+    const float pv = bf16_bits_to_f32((uint16_t)(unsigned short)pa[j]);
+    float dpv = bf16_bits_to_f32((uint16_t)(unsigned short)dpa[j]);
+    if constexpr (DROP) dpv = keep[j] ? dpv * dr.pinv : 0.f;
+    dsf[j] = pv * (dpv - di_row);
+    dsa[j] = (short)f32_to_bf16_bits(dsf[j]);
+  }
+}
 
-  f32x4 o_acc[4] = {};
+// materialize dS (BH*L, L) for the bias gradient when asked to: one 16 B store
+__device__ __forceinline__ void store_ds(uint16_t* ds_out, int64_t row, int L,
+                                         int kv, const bf16x8& dsa) {
+  if (ds_out != nullptr) {
+    union {
+      bf16x8 v;
+      uint4 u;
+    } U;
+    U.v = dsa;
+    *reinterpret_cast<uint4*>(ds_out + row * (int64_t)L + kv) = U.u;
+  }
+}
+
+// epilogue: the wave's 16 x 64 C tiles to rows row .. row+15 of (rows, HD)
+__device__ __forceinline__ void store_c_tile(uint16_t* dst, int64_t row,
+                                             const f32x4 (&acc)[4],
+                                             const Lane& ln) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb)
+      dst[(row + ln.lg * 4 + r) * (int64_t)HD + cb * 16 + ln.lr] =
+          f32_to_bf16_bits(acc[cb][r]);
+}
+
+// ===========================================================================
+// forward
+// ===========================================================================
+//
+// The forward of one block, grid (L/BM, B*H).
+// RESIDENT (L <= LRES): the whole V^T is staged once and the kv loop runs
+// barrier-free (same PMC-driven rationale as the K^T-resident dq variant).
+// Otherwise V^T is staged per tile, between two barriers.
+template <bool HAS_BIAS, bool HAS_MASK, bool DROP, bool RESIDENT>
+__device__ __forceinline__ void flash_fwd_block(
+    uint16_t* __restrict__ out, float* __restrict__ lse,
+    const uint16_t* __restrict__ qp, const uint16_t* __restrict__ kp,
+    const uint16_t* __restrict__ vp, const Src& bias, const Src& mask, int L,
+    const Drop& dr) {
+  const Lane ln = lane_coords(16);
+  const int64_t bh = blockIdx.y;
+  const int64_t row0 = bh * L + ln.row0;   // this wave's first q row
+
+  __shared__ __attribute__((aligned(16))) uint16_t lds_p[4][16][BN];
+  constexpr int VT_COLS = RESIDENT ? LRES : BN;
+  __shared__ __attribute__((aligned(16))) uint16_t lds_vt[HD][VT_COLS];
+
+  if constexpr (RESIDENT) {
+    for (int c = 0; c < L / BN; ++c)
+      stage_transposed(&lds_vt[0][0], VT_COLS, c * BN,
+                       vp + (bh * L + c * BN) * (int64_t)HD);
+    __syncthreads();
+  }
+
+  bf16x8 aq[1][2];
+  load_a(qp, row0, ln, aq[0]);
+
+  f32x4 o_acc[1][4] = {};
   float m_i[4], l_i[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
@@ -131,54 +378,34 @@ __global__ __launch_bounds__(256) void flash_fwd_vres_kernel(
     l_i[r] = 0.f;
   }
   const uint16_t* bias_rows[4];
-  const uint16_t* mask_row = nullptr;
-  if (HAS_BIAS) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int q = q0 + lg * 4 + r;
-      bias_rows[r] =
-          bias + (((bh / bias_od) % bias_nb) * bias_q + (q % bias_q)) * (int64_t)L;
-    }
-  }
-  if (HAS_MASK)
-    mask_row = mask + (((bh / mask_od) % mask_nb) * mask_q) * (int64_t)L;
+  bias_rows4<HAS_BIAS>(bias, bh, ln.row0 + ln.lg * 4, L, bias_rows);
+  const uint16_t* mask_row = mask_row_of<HAS_MASK>(mask, bh, L);
 
   const int n_tiles = L / BN;
   for (int t = 0; t < n_tiles; ++t) {
     const int kv0 = t * BN;
-    f32x4 s[4];
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb) {
-      f32x4 acc = {};
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const bf16x8 bk = load_frag(
-            kp + (bh * L + kv0 + cb * 16 + lr) * (int64_t)HD + ks * 32 + lg * 8);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq[ks], bk, acc, 0, 0, 0);
-      }
-      s[cb] = acc;
+    if constexpr (!RESIDENT) {
+      stage_transposed(&lds_vt[0][0], VT_COLS, 0,
+                       vp + (bh * L + kv0) * (int64_t)HD);
+      __syncthreads();
     }
-    if (HAS_BIAS || HAS_MASK) {
+    // ---- S = Q K^T (per wave: 16 x 64 as 4 C tiles) + bias + mask ------
+    f32x4 s[1][4];
+    score_tile<1>(aq, kp + (bh * L + kv0) * (int64_t)HD, ln, s);
+    if constexpr (HAS_BIAS || HAS_MASK) {
 #pragma unroll
-      for (int cb = 0; cb < 4; ++cb) {
-        const int kv = kv0 + cb * 16 + lr;
+      for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float add = 0.f;
-          if (HAS_BIAS)
-            add += __bfloat162float(
-                reinterpret_cast<const __hip_bfloat16*>(bias_rows[r])[kv]);
-          if (HAS_MASK)
-            add += __bfloat162float(
-                reinterpret_cast<const __hip_bfloat16*>(mask_row)[kv]);
-          s[cb][r] += add;
-        }
-      }
+        for (int r = 0; r < 4; ++r)
+          s[0][cb][r] += add_bias_mask<HAS_BIAS, HAS_MASK>(
+              0.f, bias_rows[r], mask_row, kv0 + cb * 16 + ln.lr);
     }
+    // ---- online softmax ----------------------------------------------
     float mnew[4], alpha[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      float mx = fmaxf(fmaxf(s[0][r], s[1][r]), fmaxf(s[2][r], s[3][r]));
+      float mx = fmaxf(fmaxf(s[0][0][r], s[0][1][r]),
+                       fmaxf(s[0][2][r], s[0][3][r]));
       mx = rowgroup_max(mx);
       mnew[r] = fmaxf(m_i[r], mx);
       alpha[r] = __expf(m_i[r] - mnew[r]);
@@ -189,56 +416,48 @@ __global__ __launch_bounds__(256) void flash_fwd_vres_kernel(
     for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        s[cb][r] = __expf(s[cb][r] - mnew[r]);
-        psum[r] += s[cb][r];
+        s[0][cb][r] = p_from_lse(s[0][cb][r], mnew[r]);
+        psum[r] += s[0][cb][r];
       }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       l_i[r] = l_i[r] * alpha[r] + rowgroup_sum(psum[r]);
 #pragma unroll
-      for (int cb = 0; cb < 4; ++cb) o_acc[cb][r] *= alpha[r];
+      for (int cb = 0; cb < 4; ++cb) o_acc[0][cb][r] *= alpha[r];
     }
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        lds_p[wid][lg * 4 + r][cb * 16 + lr] = f32_to_bf16_bits(s[cb][r]);
+    // ---- O += dropout(P) V -------------------------------------------
+    c_store(lds_p[ln.wid], s[0], ln);
 #pragma unroll
     for (int ks2 = 0; ks2 < 2; ++ks2) {
-      bf16x8 ap = load_frag(&lds_p[wid][lr][ks2 * 32 + lg * 8]);
-      if constexpr (DROP) {
-        bool keep[8];
-        keep_bits8<DROP>(seed, (uint64_t)(bh * L + q0 + lr),
-                         kv0 + ks2 * 32 + lg * 8, pthresh, keep);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          float pv = bf16_bits_to_f32((uint16_t)(unsigned short)ap[j]);
-          pv = keep[j] ? pv * pinv : 0.f;
-          ap[j] = (short)f32_to_bf16_bits(pv);
-        }
-      }
-#pragma unroll
-      for (int cb = 0; cb < 4; ++cb) {
-        const int d = cb * 16 + lr;
-        const bf16x8 bv = load_frag(
-            &lds_vt[d][(kv0 + ks2 * 32 + lg * 8) ^ ((d & 7) << 3)]);
-        o_acc[cb] =
-            __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap, bv, o_acc[cb], 0, 0, 0);
-      }
+      bf16x8 ap[1] = {a_load(lds_p[ln.wid], ks2, ln)};
+      drop_frag<DROP>(ap[0], dr, row0 + ln.lr, kv0 + ks2 * 32 + ln.lg * 8);
+      mma_staged<1>(ap, &lds_vt[0][0], VT_COLS,
+                    (RESIDENT ? kv0 : 0) + ks2 * 32, ln, o_acc);
     }
+    if constexpr (!RESIDENT) __syncthreads();
   }
+
+  // ---- epilogue: normalize, store O (bf16) and LSE (fp32) -------------
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const float inv = 1.0f / l_i[r];
-    const int q = q0 + lg * 4 + r;
 #pragma unroll
-    for (int cb = 0; cb < 4; ++cb)
-      out[(bh * L + q) * (int64_t)HD + cb * 16 + lr] =
-          f32_to_bf16_bits(o_acc[cb][r] * inv);
-    if (lr == 0) lse[bh * L + q] = m_i[r] + __logf(l_i[r]);
+    for (int cb = 0; cb < 4; ++cb) o_acc[0][cb][r] *= inv;
+    if (ln.lr == 0) lse[row0 + ln.lg * 4 + r] = m_i[r] + __logf(l_i[r]);
   }
+  store_c_tile(out, row0, o_acc[0], ln);
 }
 
+template <bool HAS_BIAS, bool HAS_MASK, bool DROP>
+__global__ __launch_bounds__(256) void flash_fwd_vres_kernel(
+    uint16_t* __restrict__ out, float* __restrict__ lse,
+    const uint16_t* __restrict__ qp, const uint16_t* __restrict__ kp,
+    const uint16_t* __restrict__ vp, Src bias, Src mask, int L, Drop dr) {
+  flash_fwd_block<HAS_BIAS, HAS_MASK, DROP, true>(out, lse, qp, kp, vp, bias,
+                                                  mask, L, dr);
+}
+
+// The tiled forward takes bias, mask and dropout scalars as loose arguments.
 template <bool HAS_BIAS, bool HAS_MASK, bool DROP>
 __global__ __launch_bounds__(256) void flash_fwd_kernel(
     uint16_t* __restrict__ out, float* __restrict__ lse,
@@ -247,208 +466,96 @@ __global__ __launch_bounds__(256) void flash_fwd_kernel(
     const uint16_t* __restrict__ bias, int64_t bias_nb, int bias_q, int64_t bias_od,
     const uint16_t* __restrict__ mask, int64_t mask_nb, int mask_q, int64_t mask_od,
     int L, float pinv, uint32_t pthresh, uint64_t seed) {
-  // grid: (L/BM, B*H)
-  const int qt = blockIdx.x;
-  const int64_t bh = blockIdx.y;
-  const int wid = threadIdx.x >> 6;   // wave 0..3
-  const int lane = threadIdx.x & 63;
-  const int lg = lane >> 4;           // fragment k-group / row group
-  const int lr = lane & 15;           // fragment row (A) / col (B, C)
-
-  const int q0 = qt * BM + wid * 16;  // this wave's first q row
-  const int64_t qbase = (bh * L + q0) * HD;
-
-  __shared__ __attribute__((aligned(16))) uint16_t lds_p[4][16][BN];
-  // V tile transposed [d][kv], kv XOR-swizzled in 8-element blocks keyed on
-  // d&7 so the PV B-fragment reads (different d rows, same kv range) are
-  // bank-conflict-free (guide T2 pattern)
-  __shared__ __attribute__((aligned(16))) uint16_t lds_vt[HD][BN];
-
-  // Q A-fragments (row lr, d = lg*8 + ks*32 + [0..8))
-  bf16x8 aq[2];
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks)
-    aq[ks] = load_frag(qp + qbase + (int64_t)lr * HD + ks * 32 + lg * 8);
-
-  f32x4 o_acc[4] = {};
-  float m_i[4], l_i[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    m_i[r] = -INFINITY;
-    l_i[r] = 0.f;
-  }
-
-  // bias/mask source rows for this wave's 4 C rows (rows lg*4 + r)
-  // bias element addressing (same contract as softmax_dropout):
-  //   src_row = ((bh / od) % nb) * src_q + (q % src_q)
-  const uint16_t* bias_rows[4];
-  const uint16_t* mask_row = nullptr;
-  if (HAS_BIAS) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int q = q0 + lg * 4 + r;
-      bias_rows[r] =
-          bias + (((bh / bias_od) % bias_nb) * bias_q + (q % bias_q)) * (int64_t)L;
-    }
-  }
-  if (HAS_MASK) {
-    // mask is (nb, 1, L): one row per (bh / od) batch, shared by all q
-    mask_row = mask + (((bh / mask_od) % mask_nb) * mask_q) * (int64_t)L;
-  }
-
-  // staging role: thread handles V row kv = tid/4, d block (tid%4)*16
-  const int st_kv = (int)threadIdx.x >> 2;
-  const int st_d0 = ((int)threadIdx.x & 3) * 16;
-
-  const int n_tiles = L / BN;
-  for (int t = 0; t < n_tiles; ++t) {
-    const int kv0 = t * BN;
-    // ---- stage V^T tile ----------------------------------------------
-    {
-      float f0[8], f1[8];
-      load8(reinterpret_cast<const __hip_bfloat16*>(vp) +
-                (bh * L + kv0 + st_kv) * (int64_t)HD + st_d0,
-            f0);
-      load8(reinterpret_cast<const __hip_bfloat16*>(vp) +
-                (bh * L + kv0 + st_kv) * (int64_t)HD + st_d0 + 8,
-            f1);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int d0 = st_d0 + j;
-        const int d1 = st_d0 + 8 + j;
-        lds_vt[d0][st_kv ^ ((d0 & 7) << 3)] = f32_to_bf16_bits(f0[j]);
-        lds_vt[d1][st_kv ^ ((d1 & 7) << 3)] = f32_to_bf16_bits(f1[j]);
-      }
-    }
-    __syncthreads();
-    // ---- S = Q K^T (per wave: 16 x 64 as 4 C tiles) -------------------
-    f32x4 s[4];
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb) {
-      f32x4 acc = {};
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        // B frag: col = kv0 + cb*16 + lr, k = d = ks*32 + lg*8 + [0..8)
-        const bf16x8 bk = load_frag(
-            kp + (bh * L + kv0 + cb * 16 + lr) * (int64_t)HD + ks * 32 + lg * 8);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq[ks], bk, acc, 0, 0, 0);
-      }
-      s[cb] = acc;
-    }
-    // ---- add bias / mask ---------------------------------------------
-    if (HAS_BIAS || HAS_MASK) {
-#pragma unroll
-      for (int cb = 0; cb < 4; ++cb) {
-        const int kv = kv0 + cb * 16 + lr;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float add = 0.f;
-          if (HAS_BIAS)
-            add += __bfloat162float(
-                reinterpret_cast<const __hip_bfloat16*>(bias_rows[r])[kv]);
-          if (HAS_MASK)
-            add += __bfloat162float(
-                reinterpret_cast<const __hip_bfloat16*>(mask_row)[kv]);
-          s[cb][r] += add;
-        }
-      }
-    }
-    // ---- online softmax ----------------------------------------------
-    float mnew[4], alpha[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float mx = fmaxf(fmaxf(s[0][r], s[1][r]), fmaxf(s[2][r], s[3][r]));
-      mx = rowgroup_max(mx);
-      mnew[r] = fmaxf(m_i[r], mx);
-      alpha[r] = __expf(m_i[r] - mnew[r]);
-      m_i[r] = mnew[r];
-    }
-    float psum[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        s[cb][r] = __expf(s[cb][r] - mnew[r]);
-        psum[r] += s[cb][r];
-      }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      l_i[r] = l_i[r] * alpha[r] + rowgroup_sum(psum[r]);
-#pragma unroll
-      for (int cb = 0; cb < 4; ++cb) o_acc[cb][r] *= alpha[r];
-    }
-    // ---- redistribute P (C layout) -> A layout via wave-local LDS ----
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        lds_p[wid][lg * 4 + r][cb * 16 + lr] =
-            f32_to_bf16_bits(s[cb][r]);
-    // wave-local LDS: the compiler's lgkmcnt waits order write->read within
-    // the wave; no cross-wave sharing of lds_p[wid].
-    // ---- O += dropout(P) V -------------------------------------------
-#pragma unroll
-    for (int ks2 = 0; ks2 < 2; ++ks2) {
-      // A frag of P: row = lr, cols kv = ks2*32 + lg*8 + [0..8)
-      bf16x8 ap = load_frag(&lds_p[wid][lr][ks2 * 32 + lg * 8]);
-      if constexpr (DROP) {
-        bool keep[8];
-        keep_bits8<DROP>(seed, (uint64_t)(bh * L + q0 + lr),
-                         kv0 + ks2 * 32 + lg * 8, pthresh, keep);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          float pv = bf16_bits_to_f32((uint16_t)(unsigned short)ap[j]);
-          pv = keep[j] ? pv * pinv : 0.f;
-          ap[j] = (short)f32_to_bf16_bits(pv);
-        }
-      }
-#pragma unroll
-      for (int cb = 0; cb < 4; ++cb) {
-        // B frag of V from the staged transpose: row d = cb*16+lr,
-        // kv block (ks2*32 + lg*8) ^ swizzle — one 16 B LDS read
-        const int d = cb * 16 + lr;
-        const bf16x8 bv =
-            load_frag(&lds_vt[d][(ks2 * 32 + lg * 8) ^ ((d & 7) << 3)]);
-        o_acc[cb] =
-            __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap, bv, o_acc[cb], 0, 0, 0);
-      }
-    }
-    __syncthreads();
-  }
-
-  // ---- epilogue: normalize, store O (bf16) and LSE (fp32) -------------
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const float inv = 1.0f / l_i[r];
-    const int q = q0 + lg * 4 + r;
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb)
-      out[(bh * L + q) * (int64_t)HD + cb * 16 + lr] =
-          f32_to_bf16_bits(o_acc[cb][r] * inv);
-    if (lr == 0) lse[bh * L + q] = m_i[r] + __logf(l_i[r]);
-  }
+  flash_fwd_block<HAS_BIAS, HAS_MASK, DROP, false>(
+      out, lse, qp, kp, vp, Src{bias, bias_nb, bias_q, bias_od},
+      Src{mask, mask_nb, mask_q, mask_od}, L, Drop{pinv, pthresh, seed});
 }
 
-struct SrcDesc {
-  const void* ptr = nullptr;
-  int64_t nb = 1;
-  int q = 1;
-  int64_t od = 1;
-};
-
-SrcDesc describe(const std::optional<at::Tensor>& t, int64_t outer_div, int L,
-                 const char* what) {
-  SrcDesc d;
+Src describe(const std::optional<at::Tensor>& t, int64_t outer_div, int L,
+             const char* what) {
+  Src d;
   if (t.has_value() && t->defined()) {
     TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->dim() == 3 &&
                     t->size(2) == L && t->scalar_type() == at::kBFloat16,
-                what, " must be contiguous bf16 (nb, q, L)");
-    d.ptr = t->data_ptr();
+                "flash_attn: ", what, " must be contiguous bf16 (nb, q, L=", L,
+                "), got ", t->scalar_type(), " ", t->sizes());
+    d.ptr = reinterpret_cast<const uint16_t*>(t->data_ptr());
     d.nb = t->size(0);
     d.q = (int)t->size(1);
     d.od = outer_div > 0 ? outer_div : 1;
   }
   return d;
+}
+
+// The input contract of both entries: every operand contiguous bf16
+// (BH, L, 64) on the GPU with L % 64 == 0, a mask that broadcasts over q.
+// Returns L.
+int check_inputs(const char* fn,
+                 std::initializer_list<std::pair<const char*, const at::Tensor*>>
+                     operands) {
+  const at::Tensor& q = *operands.begin()->second;
+  TORCH_CHECK(q.dim() == 3 && q.size(2) == HD, fn,
+              ": q must be (BH, L, 64), got ", q.sizes());
+  TORCH_CHECK(q.size(1) % BN == 0, fn, ": L must be a multiple of 64, got ",
+              q.size(1));
+  for (const auto& [name, t] : operands) {
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous(), fn, ": ", name,
+                " must be a contiguous GPU tensor");
+    TORCH_CHECK(t->scalar_type() == at::kBFloat16, fn, ": ", name,
+                " must be bf16, got ", t->scalar_type());
+    TORCH_CHECK(t->sizes() == q.sizes(), fn, ": ", name, " has shape ",
+                t->sizes(), ", q has ", q.sizes());
+  }
+  return (int)q.size(1);
+}
+
+Drop make_drop(bool drop, double dropout_p, uint64_t seed) {
+  Drop d;
+  if (drop) {
+    const double pc = std::min(dropout_p, 0.999999);
+    d.pinv = (float)(1.0 / (1.0 - pc));
+    d.pthresh = keep16_threshold(pc);
+  }
+  d.seed = seed;
+  return d;
+}
+
+// f(has_bias, has_mask, drop) with the three flags as std::bool_constant
+template <class F>
+void dispatch_flags(bool has_bias, bool has_mask, bool drop, F&& f) {
+  auto with_drop = [&](auto hb, auto hm) {
+    if (drop)
+      f(hb, hm, std::true_type{});
+    else
+      f(hb, hm, std::false_type{});
+  };
+  auto with_mask = [&](auto hb) {
+    if (has_mask)
+      with_drop(hb, std::true_type{});
+    else
+      with_drop(hb, std::false_type{});
+  };
+  if (has_bias)
+    with_mask(std::true_type{});
+  else
+    with_mask(std::false_type{});
+}
+
+// kernel<<<grid, 256>>>(outs..., common...): `common` is the argument pack
+// an entry builds once and every one of its kernels takes after its outputs
+template <class Kernel, class Common, class... Outs>
+void launch(Kernel* kernel, dim3 grid, hipStream_t stream, const Common& common,
+            Outs... outs) {
+  std::apply(
+      [&](auto... in) { kernel<<<grid, 256, 0, stream>>>(outs..., in...); },
+      common);
+}
+
+const uint16_t* bits(const at::Tensor& t) {
+  return reinterpret_cast<const uint16_t*>(t.data_ptr());
+}
+uint16_t* bits_mut(at::Tensor& t) {
+  return reinterpret_cast<uint16_t*>(t.data_ptr());
 }
 
 }  // namespace
@@ -460,86 +567,47 @@ std::vector<at::Tensor> flash_attn_forward(at::Tensor q, at::Tensor k, at::Tenso
                                            std::optional<at::Tensor> mask,
                                            int64_t mask_outer_div,
                                            double dropout_p, bool is_training) {
-  TORCH_CHECK(q.is_cuda() && q.is_contiguous() && k.is_contiguous() &&
-                  v.is_contiguous(),
-              "flash_attn: q/k/v must be contiguous CUDA");
-  TORCH_CHECK(q.scalar_type() == at::kBFloat16, "flash_attn: bf16 only");
-  TORCH_CHECK(q.dim() == 3 && q.size(2) == HD, "flash_attn: (BH, L, 64) only");
+  const int L =
+      check_inputs("flash_attn", {{"q", &q}, {"k", &k}, {"v", &v}});
   const int64_t BH = q.size(0);
-  const int L = (int)q.size(1);
-  TORCH_CHECK(L % BN == 0, "flash_attn: L must be a multiple of 64");
-  TORCH_CHECK(k.sizes() == q.sizes() && v.sizes() == q.sizes(), "shape mismatch");
-
-  const SrcDesc bd = describe(bias, bias_outer_div, L, "bias");
-  const SrcDesc md = describe(mask, mask_outer_div, L, "mask");
-  if (md.ptr) TORCH_CHECK(md.q == 1, "flash_attn: mask must broadcast over q");
+  const Src bd = describe(bias, bias_outer_div, L, "bias");
+  const Src md = describe(mask, mask_outer_div, L, "mask");
+  TORCH_CHECK(md.q == 1, "flash_attn: mask must broadcast over q, got q = ",
+              md.q);
 
   const bool drop = is_training && dropout_p > 0.0;
-  float pinv = 1.f;
-  uint32_t pthresh = 0;
-  uint64_t seed = 0;
-  if (drop) {
-    const double pc = std::min(dropout_p, 0.999999);
-    pinv = (float)(1.0 / (1.0 - pc));
-    pthresh = keep16_threshold(pc);
-    auto gen = at::get_generator_or_default<at::CUDAGeneratorImpl>(
-        std::nullopt, at::cuda::detail::getDefaultCUDAGenerator());
-    at::PhiloxCudaState state;
-    {
-      std::lock_guard<std::mutex> lock(gen->mutex_);
-      // counters consumed per (row) subsequence: L/4 starting at 0; the
-      // backward recomputes the same stream, so advance by the full row.
-      state = gen->philox_cuda_state((L + 3) / 4 + 4);
-    }
-    seed = state.seed_.val;
-    // NOTE: offset is intentionally NOT used — keep bits must be identical
-    // in forward and backward, and both derive them from (seed, row, kv).
-    // The generator advance still makes the NEXT op see fresh randomness.
-    seed += state.offset_.val * 0x9E3779B97F4A7C15ull;
-  }
+  // A row's keep bits consume Philox counters 0 .. L/8 - 1 of its own
+  // subsequence.  The generator is advanced by (L + 3) / 4 + 4, twice what a
+  // row needs: the figure dates from a 4-per-draw keep definition and stays,
+  // so that the ops after this one draw what they always drew.
+  // The offset is folded into the seed and otherwise NOT used — keep bits
+  // must be identical in forward and backward, and both derive them from
+  // (seed, row, kv).  The generator advance still makes the NEXT op see
+  // fresh randomness.
+  const uint64_t seed = drop ? reserve_philox_key((L + 3) / 4 + 4) : 0;
+  const Drop dr = make_drop(drop, dropout_p, seed);
 
   auto o = at::empty_like(q);
   auto lse_t = at::empty({BH, (int64_t)L}, q.options().dtype(at::kFloat));
   auto stream = at::cuda::getCurrentCUDAStream();
   const dim3 grid(L / BM, BH);
+  const auto common = std::make_tuple(bits(q), bits(k), bits(v), bd, md, L, dr);
+  // the tiled kernel takes the same values as loose arguments
+  const auto loose = std::make_tuple(bits(q), bits(k), bits(v), bd.ptr, bd.nb,
+                                     bd.q, bd.od, md.ptr, md.nb, md.q, md.od, L,
+                                     dr.pinv, dr.pthresh, dr.seed);
 
-  auto launch = [&](auto has_bias, auto has_mask, auto dropt) {
-    constexpr bool HB = decltype(has_bias)::value;
-    constexpr bool HM = decltype(has_mask)::value;
-    constexpr bool DR = decltype(dropt)::value;
-    if (L <= 512)
-      flash_fwd_vres_kernel<HB, HM, DR, 512><<<grid, 256, 0, stream>>>(
-          reinterpret_cast<uint16_t*>(o.data_ptr()), lse_t.data_ptr<float>(),
-          reinterpret_cast<const uint16_t*>(q.data_ptr()),
-          reinterpret_cast<const uint16_t*>(k.data_ptr()),
-          reinterpret_cast<const uint16_t*>(v.data_ptr()),
-          reinterpret_cast<const uint16_t*>(bd.ptr), bd.nb, bd.q, bd.od,
-          reinterpret_cast<const uint16_t*>(md.ptr), md.nb, md.q, md.od, L,
-          pinv, pthresh, seed);
+  dispatch_flags(bd.ptr, md.ptr, drop, [&](auto hb, auto hm, auto dt) {
+    constexpr bool HB = decltype(hb)::value;
+    constexpr bool HM = decltype(hm)::value;
+    constexpr bool DR = decltype(dt)::value;
+    if (L <= LRES)
+      launch(flash_fwd_vres_kernel<HB, HM, DR>, grid, stream, common,
+             bits_mut(o), lse_t.data_ptr<float>());
     else
-      flash_fwd_kernel<HB, HM, DR><<<grid, 256, 0, stream>>>(
-          reinterpret_cast<uint16_t*>(o.data_ptr()), lse_t.data_ptr<float>(),
-          reinterpret_cast<const uint16_t*>(q.data_ptr()),
-          reinterpret_cast<const uint16_t*>(k.data_ptr()),
-          reinterpret_cast<const uint16_t*>(v.data_ptr()),
-          reinterpret_cast<const uint16_t*>(bd.ptr), bd.nb, bd.q, bd.od,
-          reinterpret_cast<const uint16_t*>(md.ptr), md.nb, md.q, md.od, L,
-          pinv, pthresh, seed);
-  };
-  auto pick = [&](auto has_bias, auto has_mask) {
-    if (drop)
-      launch(has_bias, has_mask, std::true_type{});
-    else
-      launch(has_bias, has_mask, std::false_type{});
-  };
-  if (bd.ptr && md.ptr)
-    pick(std::true_type{}, std::true_type{});
-  else if (bd.ptr)
-    pick(std::true_type{}, std::false_type{});
-  else if (md.ptr)
-    pick(std::false_type{}, std::true_type{});
-  else
-    pick(std::false_type{}, std::false_type{});
+      launch(flash_fwd_kernel<HB, HM, DR>, grid, stream, loose, bits_mut(o),
+             lse_t.data_ptr<float>());
+  });
   C10_CUDA_KERNEL_LAUNCH_CHECK();
   // seed is host-side state: keep it on CPU so `int(seed)` in the autograd
   // wrapper is free (a CUDA scalar here cost a D2H sync per forward and
@@ -584,385 +652,32 @@ __global__ void flash_dot_do_o_kernel(float* __restrict__ di,
   }
 }
 
-// K^T-resident dq variant (L <= 1024): the whole K^T tile is staged once
-// (L*HD bf16 <= 128 KB LDS) so the kv loop runs with NO per-tile barriers —
-// the per-tile barrier+staging serialization is what keeps the tiled dq
-// kernel at ~2%% MFMA utilization (PMC evidence in profiles/).
-template <bool HAS_BIAS, bool HAS_MASK, bool DROP, int LMAX>
-__global__ __launch_bounds__(256) void flash_bwd_dq_kres_kernel(
-    uint16_t* __restrict__ dq, uint16_t* __restrict__ ds_out,
-    const uint16_t* __restrict__ dop, const uint16_t* __restrict__ qp,
-    const uint16_t* __restrict__ kp, const uint16_t* __restrict__ vp,
-    const float* __restrict__ lse, const float* __restrict__ di,
-    const uint16_t* __restrict__ bias, int64_t bias_nb, int bias_q, int64_t bias_od,
-    const uint16_t* __restrict__ mask, int64_t mask_nb, int mask_q, int64_t mask_od,
-    int L, float pinv, uint32_t pthresh, uint64_t seed) {
-  const int qt = blockIdx.x;
-  const int64_t bh = blockIdx.y;
-  const int wid = threadIdx.x >> 6;
-  const int lane = threadIdx.x & 63;
-  const int lg = lane >> 4;
-  const int lr = lane & 15;
-  const int q0 = qt * BM + wid * 16;
-  const int64_t qbase = (bh * L + q0) * HD;
+// The atomic dbias accumulator is an argument of the tiled dq kernel only:
+// merely carrying the never-taken branch in a short-L kernel cost 8 VGPRs
+// and an occupancy step (docs/KERNELS.md, "Flash dbias fusion").
+struct NoDbiasAcc {};
+template <bool RESIDENT>
+using DbiasAcc = std::conditional_t<RESIDENT, NoDbiasAcc, float*>;
 
-  __shared__ __attribute__((aligned(16))) uint16_t lds_t[4][2][16][BN];
-  __shared__ __attribute__((aligned(16))) uint16_t lds_kt[HD][LMAX];
-
-  // stage the WHOLE K^T once: thread covers kv rows tid/4 + 64*c
-  {
-    const int st_kv0 = (int)threadIdx.x >> 2;
-    const int st_d0 = ((int)threadIdx.x & 3) * 16;
-    for (int c = 0; c < L / 64; ++c) {
-      const int kv = st_kv0 + c * 64;
-      float f0[8], f1[8];
-      load8(reinterpret_cast<const __hip_bfloat16*>(kp) +
-                (bh * L + kv) * (int64_t)HD + st_d0,
-            f0);
-      load8(reinterpret_cast<const __hip_bfloat16*>(kp) +
-                (bh * L + kv) * (int64_t)HD + st_d0 + 8,
-            f1);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int d0 = st_d0 + j;
-        const int d1 = st_d0 + 8 + j;
-        lds_kt[d0][kv ^ ((d0 & 7) << 3)] = f32_to_bf16_bits(f0[j]);
-        lds_kt[d1][kv ^ ((d1 & 7) << 3)] = f32_to_bf16_bits(f1[j]);
-      }
-    }
-  }
-  __syncthreads();
-
-  bf16x8 aq[2], ado[2];
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks) {
-    aq[ks] = load_frag(qp + qbase + (int64_t)lr * HD + ks * 32 + lg * 8);
-    ado[ks] = load_frag(dop + qbase + (int64_t)lr * HD + ks * 32 + lg * 8);
-  }
-  float lse_r[4], di_r[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    lse_r[r] = lse[bh * L + q0 + lg * 4 + r];
-    di_r[r] = di[bh * L + q0 + lg * 4 + r];
-  }
-  const float di_row = di[bh * L + q0 + lr];
-  const uint16_t* bias_rows[4];
-  const uint16_t* mask_row = nullptr;
-  if (HAS_BIAS) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int q = q0 + lg * 4 + r;
-      bias_rows[r] =
-          bias + (((bh / bias_od) % bias_nb) * bias_q + (q % bias_q)) * (int64_t)L;
-    }
-  }
-  if (HAS_MASK)
-    mask_row = mask + (((bh / mask_od) % mask_nb) * mask_q) * (int64_t)L;
-
-  f32x4 dq_acc[4] = {};
-  const int n_tiles = L / BN;
-  for (int t = 0; t < n_tiles; ++t) {
-    const int kv0 = t * BN;
-    f32x4 s[4], dp[4];
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb) {
-      f32x4 acc = {}, accd = {};
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const bf16x8 bk = load_frag(
-            kp + (bh * L + kv0 + cb * 16 + lr) * (int64_t)HD + ks * 32 + lg * 8);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq[ks], bk, acc, 0, 0, 0);
-        const bf16x8 bvt = load_frag(
-            vp + (bh * L + kv0 + cb * 16 + lr) * (int64_t)HD + ks * 32 + lg * 8);
-        accd = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ado[ks], bvt, accd, 0, 0, 0);
-      }
-      s[cb] = acc;
-      dp[cb] = accd;
-    }
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb) {
-      const int kv = kv0 + cb * 16 + lr;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float sv = s[cb][r];
-        if (HAS_BIAS)
-          sv += __bfloat162float(
-              reinterpret_cast<const __hip_bfloat16*>(bias_rows[r])[kv]);
-        if (HAS_MASK)
-          sv += __bfloat162float(
-              reinterpret_cast<const __hip_bfloat16*>(mask_row)[kv]);
-        s[cb][r] = __expf(sv - lse_r[r]);
-      }
-    }
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        lds_t[wid][0][lg * 4 + r][cb * 16 + lr] = f32_to_bf16_bits(s[cb][r]);
-        lds_t[wid][1][lg * 4 + r][cb * 16 + lr] = f32_to_bf16_bits(dp[cb][r]);
-      }
-#pragma unroll
-    for (int ks2 = 0; ks2 < 2; ++ks2) {
-      const bf16x8 pa = load_frag(&lds_t[wid][0][lr][ks2 * 32 + lg * 8]);
-      const bf16x8 dpa = load_frag(&lds_t[wid][1][lr][ks2 * 32 + lg * 8]);
-      bool keep[8];
-      keep_bits8<DROP>(seed, (uint64_t)(bh * L + q0 + lr),
-                       kv0 + ks2 * 32 + lg * 8, pthresh, keep);
-      bf16x8 dsa;
-      float dsf[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float pv = bf16_bits_to_f32((uint16_t)(unsigned short)pa[j]);
-        float dpv = bf16_bits_to_f32((uint16_t)(unsigned short)dpa[j]);
-        if (DROP) dpv = keep[j] ? dpv * pinv : 0.f;
-        dsf[j] = pv * (dpv - di_row);
-        dsa[j] = (short)f32_to_bf16_bits(dsf[j]);
-      }
-      if (ds_out != nullptr) {
-        union {
-          bf16x8 v;
-          uint4 u;
-        } U;
-        U.v = dsa;
-        *reinterpret_cast<uint4*>(ds_out + (bh * L + q0 + lr) * (int64_t)L +
-                                  kv0 + ks2 * 32 + lg * 8) = U.u;
-      }
-#pragma unroll
-      for (int cb = 0; cb < 4; ++cb) {
-        const int d = cb * 16 + lr;
-        const bf16x8 bkf = load_frag(
-            &lds_kt[d][(kv0 + ks2 * 32 + lg * 8) ^ ((d & 7) << 3)]);
-        dq_acc[cb] =
-            __builtin_amdgcn_mfma_f32_16x16x32_bf16(dsa, bkf, dq_acc[cb], 0, 0, 0);
-      }
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int q = q0 + lg * 4 + r;
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb)
-      dq[(bh * L + q) * (int64_t)HD + cb * 16 + lr] =
-          f32_to_bf16_bits(dq_acc[cb][r]);
-  }
-}
-
-// 32-row-per-wave K-resident dq (L % 128 == 0, L <= 1024): each wave owns
-// TWO 16-row M-tiles, so every K/V B-fragment load feeds two MFMAs and the
-// per-tile scalar overheads (lse/di/bias addressing, philox) amortize.
-// P/dS redistribute shares one LDS buffer sequentially (wave-local order).
-template <bool HAS_BIAS, bool HAS_MASK, bool DROP, int LMAX>
-__global__ __launch_bounds__(256) void flash_bwd_dq_k32_kernel(
-    uint16_t* __restrict__ dq, uint16_t* __restrict__ ds_out,
-    const uint16_t* __restrict__ dop, const uint16_t* __restrict__ qp,
-    const uint16_t* __restrict__ kp, const uint16_t* __restrict__ vp,
-    const float* __restrict__ lse, const float* __restrict__ di,
-    const uint16_t* __restrict__ bias, int64_t bias_nb, int bias_q, int64_t bias_od,
-    const uint16_t* __restrict__ mask, int64_t mask_nb, int mask_q, int64_t mask_od,
-    int L, float pinv, uint32_t pthresh, uint64_t seed) {
-  const int qt = blockIdx.x;
-  const int64_t bh = blockIdx.y;
-  const int wid = threadIdx.x >> 6;
-  const int lane = threadIdx.x & 63;
-  const int lg = lane >> 4;
-  const int lr = lane & 15;
-  const int q0 = qt * 128 + wid * 32;   // wave's first q row (2 M-tiles)
-
-  // K^T is staged per kv-tile (8 KB) instead of full-L resident (64 KB):
-  // the resident version capped the block at 80 KB LDS -> 2 blocks/CU ->
-  // 2 waves/SIMD, and PMC showed 41% of wave cycles parked on waits —
-  // occupancy, not staging traffic, was the binding constraint.
-  __shared__ __attribute__((aligned(16))) uint16_t lds_t[4][2][16][BN];
-  __shared__ __attribute__((aligned(16))) uint16_t lds_kt[2][HD][BN];
-  const int st_kv0 = (int)threadIdx.x >> 2;
-  const int st_d0 = ((int)threadIdx.x & 3) * 16;
-
-  bf16x8 aq[2][2], ado[2][2];
-  float lse_r[2][4], di_r[2][4], di_row[2];
-  const uint16_t* bias_rows[2][4];
-  const uint16_t* mask_row = nullptr;
-#pragma unroll
-  for (int mtile = 0; mtile < 2; ++mtile) {
-    const int64_t qbase = (bh * L + q0 + mtile * 16) * (int64_t)HD;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      aq[mtile][ks] = load_frag(qp + qbase + (int64_t)lr * HD + ks * 32 + lg * 8);
-      ado[mtile][ks] = load_frag(dop + qbase + (int64_t)lr * HD + ks * 32 + lg * 8);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int q = q0 + mtile * 16 + lg * 4 + r;
-      lse_r[mtile][r] = lse[bh * L + q];
-      di_r[mtile][r] = di[bh * L + q];
-      if (HAS_BIAS)
-        bias_rows[mtile][r] =
-            bias +
-            (((bh / bias_od) % bias_nb) * bias_q + (q % bias_q)) * (int64_t)L;
-    }
-    di_row[mtile] = di[bh * L + q0 + mtile * 16 + lr];
-  }
-  if (HAS_MASK)
-    mask_row = mask + (((bh / mask_od) % mask_nb) * mask_q) * (int64_t)L;
-
-  f32x4 dq_acc[2][4] = {};
-  const int n_tiles = L / BN;
-  // NOTE (measured): a T14 register prefetch of the next tile's K/V
-  // fragments was tried here (issue after the bias loads, single register
-  // set) — dq went 630 -> 832-1099 us. At 264+ VGPR / 1 wave/SIMD the
-  // extra 96 registers hurt scheduling more than the ~500-cycle load
-  // latency costs; the FIFO vm-queue also forces later short loads to
-  // drain any outstanding prefetch. Reverted; kept as a record.
-  // ping-pong K^T staging: stage tile t+1 into the other buffer while
-  // computing tile t, one barrier per iteration
-  auto stage_kt = [&](int tile) {
-    const int kv = tile * BN + st_kv0;
-    uint16_t* buf = &lds_kt[tile & 1][0][0];
-    float f0[8], f1[8];
-    load8(reinterpret_cast<const __hip_bfloat16*>(kp) +
-              (bh * L + kv) * (int64_t)HD + st_d0,
-          f0);
-    load8(reinterpret_cast<const __hip_bfloat16*>(kp) +
-              (bh * L + kv) * (int64_t)HD + st_d0 + 8,
-          f1);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int d0 = st_d0 + j;
-      const int d1 = st_d0 + 8 + j;
-      buf[d0 * BN + (st_kv0 ^ ((d0 & 7) << 3))] = f32_to_bf16_bits(f0[j]);
-      buf[d1 * BN + (st_kv0 ^ ((d1 & 7) << 3))] = f32_to_bf16_bits(f1[j]);
-    }
-  };
-  stage_kt(0);
-  __syncthreads();
-  for (int t = 0; t < n_tiles; ++t) {
-    const int kv0 = t * BN;
-    if (t + 1 < n_tiles) stage_kt(t + 1);
-    f32x4 s[2][4], dp[2][4];
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb) {
-      f32x4 acc0 = {}, acc1 = {}, accd0 = {}, accd1 = {};
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const bf16x8 bk = load_frag(
-            kp + (bh * L + kv0 + cb * 16 + lr) * (int64_t)HD + ks * 32 + lg * 8);
-        const bf16x8 bvt = load_frag(
-            vp + (bh * L + kv0 + cb * 16 + lr) * (int64_t)HD + ks * 32 + lg * 8);
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq[0][ks], bk, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aq[1][ks], bk, acc1, 0, 0, 0);
-        accd0 =
-            __builtin_amdgcn_mfma_f32_16x16x32_bf16(ado[0][ks], bvt, accd0, 0, 0, 0);
-        accd1 =
-            __builtin_amdgcn_mfma_f32_16x16x32_bf16(ado[1][ks], bvt, accd1, 0, 0, 0);
-      }
-      s[0][cb] = acc0;
-      s[1][cb] = acc1;
-      dp[0][cb] = accd0;
-      dp[1][cb] = accd1;
-    }
-    __builtin_amdgcn_s_setprio(0);
-#pragma unroll
-    for (int mtile = 0; mtile < 2; ++mtile)
-#pragma unroll
-      for (int cb = 0; cb < 4; ++cb) {
-        const int kv = kv0 + cb * 16 + lr;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float sv = s[mtile][cb][r];
-          if (HAS_BIAS)
-            sv += __bfloat162float(reinterpret_cast<const __hip_bfloat16*>(
-                bias_rows[mtile][r])[kv]);
-          if (HAS_MASK)
-            sv += __bfloat162float(
-                reinterpret_cast<const __hip_bfloat16*>(mask_row)[kv]);
-          s[mtile][cb][r] = __expf(sv - lse_r[mtile][r]);
-        }
-      }
-    // redistribute P (both M-tiles), read A-fragments, then reuse for dS
-#pragma unroll
-    for (int mtile = 0; mtile < 2; ++mtile)
-#pragma unroll
-      for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          lds_t[wid][mtile][lg * 4 + r][cb * 16 + lr] =
-              f32_to_bf16_bits(s[mtile][cb][r]);
-    bf16x8 pa[2][2];
-#pragma unroll
-    for (int mtile = 0; mtile < 2; ++mtile)
-#pragma unroll
-      for (int ks2 = 0; ks2 < 2; ++ks2)
-        pa[mtile][ks2] = load_frag(&lds_t[wid][mtile][lr][ks2 * 32 + lg * 8]);
-#pragma unroll
-    for (int mtile = 0; mtile < 2; ++mtile)
-#pragma unroll
-      for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          lds_t[wid][mtile][lg * 4 + r][cb * 16 + lr] =
-              f32_to_bf16_bits(dp[mtile][cb][r]);
-#pragma unroll
-    for (int ks2 = 0; ks2 < 2; ++ks2) {
-      bool keep[2][8];
-      bf16x8 dsa[2];
-#pragma unroll
-      for (int mtile = 0; mtile < 2; ++mtile) {
-        const bf16x8 dpa =
-            load_frag(&lds_t[wid][mtile][lr][ks2 * 32 + lg * 8]);
-        keep_bits8<DROP>(seed, (uint64_t)(bh * L + q0 + mtile * 16 + lr),
-                         kv0 + ks2 * 32 + lg * 8, pthresh, keep[mtile]);
-        float dsf[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float pv =
-              bf16_bits_to_f32((uint16_t)(unsigned short)pa[mtile][ks2][j]);
-          float dpv = bf16_bits_to_f32((uint16_t)(unsigned short)dpa[j]);
-          if (DROP) dpv = keep[mtile][j] ? dpv * pinv : 0.f;
-          dsf[j] = pv * (dpv - di_row[mtile]);
-          dsa[mtile][j] = (short)f32_to_bf16_bits(dsf[j]);
-        }
-        if (ds_out != nullptr) {
-          union {
-            bf16x8 v;
-            uint4 u;
-          } U;
-          U.v = dsa[mtile];
-          *reinterpret_cast<uint4*>(
-              ds_out + (bh * L + q0 + mtile * 16 + lr) * (int64_t)L + kv0 +
-              ks2 * 32 + lg * 8) = U.u;
-        }
-      }
-#pragma unroll
-      for (int cb = 0; cb < 4; ++cb) {
-        const int d = cb * 16 + lr;
-        const bf16x8 bkf = load_frag(
-            &lds_kt[t & 1][d][(ks2 * 32 + lg * 8) ^ ((d & 7) << 3)]);
-        dq_acc[0][cb] =
-            __builtin_amdgcn_mfma_f32_16x16x32_bf16(dsa[0], bkf, dq_acc[0][cb], 0, 0, 0);
-        dq_acc[1][cb] =
-            __builtin_amdgcn_mfma_f32_16x16x32_bf16(dsa[1], bkf, dq_acc[1][cb], 0, 0, 0);
-      }
-    }
-    // publish tile t+1's staging; reads of buffer t&1 are also done, so
-    // its restage at t+2 (after the next barrier) is safe
-    __syncthreads();
-  }
-#pragma unroll
-  for (int mtile = 0; mtile < 2; ++mtile)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int q = q0 + mtile * 16 + lg * 4 + r;
-#pragma unroll
-      for (int cb = 0; cb < 4; ++cb)
-        dq[(bh * L + q) * (int64_t)HD + cb * 16 + lr] =
-            f32_to_bf16_bits(dq_acc[mtile][cb][r]);
-    }
-}
-
-template <bool HAS_BIAS, bool HAS_MASK, bool DROP>
+// dQ, 16 q rows per wave.
+// RESIDENT (L <= LRES with L % 128 != 0; profiles call it dq_kres): the
+// whole K^T is staged once (L*HD bf16 <= 64 KB LDS) so the kv loop runs with
+// NO per-tile barriers — the per-tile barrier+staging serialization is what
+// keeps the tiled variant at ~2%% MFMA utilization (PMC evidence in
+// profiles/).  Otherwise (L > LRES) K^T is staged per tile, and dS can be
+// accumulated into dbias_acc with atomics (run-time null check).
+// The body keeps its statements written out, in the order they had before
+// the shared blocks existed, and loose bias / mask / dropout arguments:
+// assembled from score_tile, p_tile, c_store / a_load, ds_frag and
+// mma_staged it took 148-156 VGPRs where this text takes 120-128 (a wave
+// per SIMD less) and its backward ran 9.3% slower with mask + dropout at
+// L 1024.  swz is the one block it shares: with Lane, Src::row, store_ds and
+// store_c_tile as well, the RESIDENT instantiations 001 / 010 took 132 VGPRs
+// against 128, again a wave less.
+template <bool HAS_BIAS, bool HAS_MASK, bool DROP, bool RESIDENT>
 __global__ __launch_bounds__(256) void flash_bwd_dq_kernel(
     uint16_t* __restrict__ dq, uint16_t* __restrict__ ds_out,
-    float* __restrict__ dbias_acc,
+    DbiasAcc<RESIDENT> dbias_acc,
     const uint16_t* __restrict__ dop,
     const uint16_t* __restrict__ qp, const uint16_t* __restrict__ kp,
     const uint16_t* __restrict__ vp, const float* __restrict__ lse,
@@ -982,9 +697,35 @@ __global__ __launch_bounds__(256) void flash_bwd_dq_kernel(
   // [wave][0]=P tile, [wave][1]=dS tile (C-layout write, A-layout read)
   __shared__ __attribute__((aligned(16))) uint16_t lds_t[4][2][16][BN];
   // K tile transposed [d][kv] (swizzled) for the dQ = dS K product
-  __shared__ __attribute__((aligned(16))) uint16_t lds_kt[HD][BN];
+  __shared__ __attribute__((aligned(16))) uint16_t lds_kt[HD][RESIDENT ? LRES : BN];
   const int st_kv = (int)threadIdx.x >> 2;
   const int st_d0 = ((int)threadIdx.x & 3) * 16;
+
+  if constexpr (RESIDENT) {
+    // stage the WHOLE K^T once: thread covers kv rows tid/4 + 64*c
+    {
+      const int st_kv0 = (int)threadIdx.x >> 2;
+      const int st_d0 = ((int)threadIdx.x & 3) * 16;
+      for (int c = 0; c < L / 64; ++c) {
+        const int kv = st_kv0 + c * 64;
+        float f0[8], f1[8];
+        load8(reinterpret_cast<const __hip_bfloat16*>(kp) +
+                  (bh * L + kv) * (int64_t)HD + st_d0,
+              f0);
+        load8(reinterpret_cast<const __hip_bfloat16*>(kp) +
+                  (bh * L + kv) * (int64_t)HD + st_d0 + 8,
+              f1);
+  #pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int d0 = st_d0 + j;
+          const int d1 = st_d0 + 8 + j;
+          lds_kt[d0][swz(d0, kv)] = f32_to_bf16_bits(f0[j]);
+          lds_kt[d1][swz(d1, kv)] = f32_to_bf16_bits(f1[j]);
+        }
+      }
+    }
+    __syncthreads();
+  }
 
   bf16x8 aq[2], ado[2];
 #pragma unroll
@@ -992,11 +733,10 @@ __global__ __launch_bounds__(256) void flash_bwd_dq_kernel(
     aq[ks] = load_frag(qp + qbase + (int64_t)lr * HD + ks * 32 + lg * 8);
     ado[ks] = load_frag(dop + qbase + (int64_t)lr * HD + ks * 32 + lg * 8);
   }
-  float lse_r[4], di_r[4];
+  float lse_r[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     lse_r[r] = lse[bh * L + q0 + lg * 4 + r];
-    di_r[r] = di[bh * L + q0 + lg * 4 + r];
   }
   const float di_row = di[bh * L + q0 + lr];   // Di for this lane's A row
   const uint16_t* bias_rows[4];
@@ -1016,23 +756,25 @@ __global__ __launch_bounds__(256) void flash_bwd_dq_kernel(
   const int n_tiles = L / BN;
   for (int t = 0; t < n_tiles; ++t) {
     const int kv0 = t * BN;
-    {
-      float f0[8], f1[8];
-      load8(reinterpret_cast<const __hip_bfloat16*>(kp) +
-                (bh * L + kv0 + st_kv) * (int64_t)HD + st_d0,
-            f0);
-      load8(reinterpret_cast<const __hip_bfloat16*>(kp) +
-                (bh * L + kv0 + st_kv) * (int64_t)HD + st_d0 + 8,
-            f1);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int d0 = st_d0 + j;
-        const int d1 = st_d0 + 8 + j;
-        lds_kt[d0][st_kv ^ ((d0 & 7) << 3)] = f32_to_bf16_bits(f0[j]);
-        lds_kt[d1][st_kv ^ ((d1 & 7) << 3)] = f32_to_bf16_bits(f1[j]);
+    if constexpr (!RESIDENT) {
+      {
+        float f0[8], f1[8];
+        load8(reinterpret_cast<const __hip_bfloat16*>(kp) +
+                  (bh * L + kv0 + st_kv) * (int64_t)HD + st_d0,
+              f0);
+        load8(reinterpret_cast<const __hip_bfloat16*>(kp) +
+                  (bh * L + kv0 + st_kv) * (int64_t)HD + st_d0 + 8,
+              f1);
+  #pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int d0 = st_d0 + j;
+          const int d1 = st_d0 + 8 + j;
+          lds_kt[d0][swz(d0, st_kv)] = f32_to_bf16_bits(f0[j]);
+          lds_kt[d1][swz(d1, st_kv)] = f32_to_bf16_bits(f1[j]);
+        }
       }
+      __syncthreads();
     }
-    __syncthreads();
     f32x4 s[4], dp[4];
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb) {
@@ -1090,8 +832,9 @@ __global__ __launch_bounds__(256) void flash_bwd_dq_kernel(
         dsf[j] = pv * (dpv - di_row);
         dsa[j] = (short)f32_to_bf16_bits(dsf[j]);
       }
-      if (HAS_BIAS && dbias_acc != nullptr) {
-        // fused dbias accumulation (see kres variant)
+      if constexpr (!RESIDENT) if (HAS_BIAS && dbias_acc != nullptr) {
+        // fused dbias accumulation: fp32 dS straight into the (nb, L, L)
+        // buffer; contention equals the broadcast batch count
         const int64_t brow =
             ((bh / bias_od) % bias_nb) * (int64_t)bias_q + ((q0 + lr) % bias_q);
         float* bdst = dbias_acc + brow * (int64_t)L + kv0 + ks2 * 32 + lg * 8;
@@ -1113,12 +856,12 @@ __global__ __launch_bounds__(256) void flash_bwd_dq_kernel(
       for (int cb = 0; cb < 4; ++cb) {
         const int d = cb * 16 + lr;
         const bf16x8 bkf =
-            load_frag(&lds_kt[d][(ks2 * 32 + lg * 8) ^ ((d & 7) << 3)]);
+            load_frag(&lds_kt[d][swz(d, (RESIDENT ? kv0 : 0) + ks2 * 32 + lg * 8)]);
         dq_acc[cb] =
             __builtin_amdgcn_mfma_f32_16x16x32_bf16(dsa, bkf, dq_acc[cb], 0, 0, 0);
       }
     }
-    __syncthreads();
+    if constexpr (!RESIDENT) __syncthreads();
   }
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
@@ -1130,389 +873,231 @@ __global__ __launch_bounds__(256) void flash_bwd_dq_kernel(
   }
 }
 
-// Q^T/dO^T-hybrid dkv variant (L <= 512): dO^T staged fully (the q loop
-// runs without per-tile dO staging barriers); the P/dS redistribute buffer
-// is shared sequentially (wave-local ordering), keeping the block at
-// <= 80 KB LDS for 2 blocks/CU.
-// Q^T/dO^T-hybrid dkv variant (L <= 512): dO^T staged fully (the q loop
-// runs without per-tile dO staging barriers); the P/dS redistribute buffer
-// is shared sequentially (wave-local ordering), keeping the block at
-// <= 80 KB LDS for 2 blocks/CU.
-// 32-kv-row-per-wave dkv (L % 128 == 0, L <= 512): two kv M-tiles per
-// wave — every Q/dO B-fragment and the staged lds_qt/lds_dot reads feed
-// two MFMAs; per-q-tile staging barriers amortize over 2x the math.
-template <bool HAS_BIAS, bool HAS_MASK, bool DROP, int LMAX>
-__global__ __launch_bounds__(256) void flash_bwd_dkv_q32_kernel(
-    uint16_t* __restrict__ dk, uint16_t* __restrict__ dv,
+// 32-row-per-wave dq (L % 128 == 0, L <= LRES): each wave owns TWO 16-row
+// M-tiles, so every K/V B-fragment load feeds two MFMAs and the per-tile
+// scalar overheads (lse/di/bias addressing, philox) amortize.
+// P/dS redistribute shares one LDS buffer sequentially (wave-local order).
+template <bool HAS_BIAS, bool HAS_MASK, bool DROP>
+__global__ __launch_bounds__(256) void flash_bwd_dq_k32_kernel(
+    uint16_t* __restrict__ dq, uint16_t* __restrict__ ds_out,
     const uint16_t* __restrict__ dop, const uint16_t* __restrict__ qp,
     const uint16_t* __restrict__ kp, const uint16_t* __restrict__ vp,
-    const float* __restrict__ lse, const float* __restrict__ di,
-    const uint16_t* __restrict__ bias, int64_t bias_nb, int bias_q, int64_t bias_od,
-    const uint16_t* __restrict__ mask, int64_t mask_nb, int mask_q, int64_t mask_od,
-    int L, float pinv, uint32_t pthresh, uint64_t seed) {
-  const int kt = blockIdx.x;
+    const float* __restrict__ lse, const float* __restrict__ di, Src bias,
+    Src mask, int L, Drop dr) {
+  const Lane ln = lane_coords(32);   // 2 M-tiles
   const int64_t bh = blockIdx.y;
-  const int wid = threadIdx.x >> 6;
-  const int lane = threadIdx.x & 63;
-  const int lg = lane >> 4;
-  const int lr = lane & 15;
-  const int kv0w = kt * 128 + wid * 32;   // wave's first kv row (2 M-tiles)
 
+  // K^T is staged per kv-tile (8 KB) instead of full-L resident (64 KB):
+  // the resident version capped the block at 80 KB LDS -> 2 blocks/CU ->
+  // 2 waves/SIMD, and PMC showed 41% of wave cycles parked on waits —
+  // occupancy, not staging traffic, was the binding constraint.
   __shared__ __attribute__((aligned(16))) uint16_t lds_t[4][2][16][BN];
-  __shared__ __attribute__((aligned(16))) uint16_t lds_dot[HD][LMAX];
-  __shared__ __attribute__((aligned(16))) uint16_t lds_qt[HD][BM];
-  const int st_q0 = (int)threadIdx.x >> 2;
-  const int st_d0 = ((int)threadIdx.x & 3) * 16;
+  __shared__ __attribute__((aligned(16))) uint16_t lds_kt[2][HD][BN];
 
-  {
-    for (int c = 0; c < L / 64; ++c) {
-      const int qq = st_q0 + c * 64;
-      const int64_t row = (bh * L + qq) * (int64_t)HD;
-      float f0[8], f1[8];
-      load8(reinterpret_cast<const __hip_bfloat16*>(dop) + row + st_d0, f0);
-      load8(reinterpret_cast<const __hip_bfloat16*>(dop) + row + st_d0 + 8, f1);
+  bf16x8 aq[2][2], ado[2][2];
+  float lse_r[2][4], di_row[2];
+  const uint16_t* bias_rows[2][4];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int d0 = st_d0 + j;
-        const int d1 = st_d0 + 8 + j;
-        lds_dot[d0][qq ^ ((d0 & 7) << 3)] = f32_to_bf16_bits(f0[j]);
-        lds_dot[d1][qq ^ ((d1 & 7) << 3)] = f32_to_bf16_bits(f1[j]);
-      }
-    }
+  for (int mtile = 0; mtile < 2; ++mtile) {
+    const int64_t row = bh * L + ln.row0 + mtile * 16;
+    load_a(qp, row, ln, aq[mtile]);
+    load_a(dop, row, ln, ado[mtile]);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) lse_r[mtile][r] = lse[row + ln.lg * 4 + r];
+    bias_rows4<HAS_BIAS>(bias, bh, ln.row0 + mtile * 16 + ln.lg * 4, L,
+                         bias_rows[mtile]);
+    di_row[mtile] = di[row + ln.lr];
   }
+  const uint16_t* mask_row = mask_row_of<HAS_MASK>(mask, bh, L);
+
+  f32x4 dq_acc[2][4] = {};
+  const int n_tiles = L / BN;
+  // NOTE (measured): a T14 register prefetch of the next tile's K/V
+  // fragments was tried here (issue after the bias loads, single register
+  // set) — dq went 630 -> 832-1099 us. At 264+ VGPR / 1 wave/SIMD the
+  // extra 96 registers hurt scheduling more than the ~500-cycle load
+  // latency costs; the FIFO vm-queue also forces later short loads to
+  // drain any outstanding prefetch. Reverted; kept as a record.
+  // ping-pong K^T staging: stage tile t+1 into the other buffer while
+  // computing tile t, one barrier per iteration
+  stage_transposed(&lds_kt[0][0][0], BN, 0, kp + bh * L * (int64_t)HD);
   __syncthreads();
-
-  bf16x8 ak[2][2], av[2][2];
-  float maskv[2][4];
+  for (int t = 0; t < n_tiles; ++t) {
+    const int kv0 = t * BN;
+    if (t + 1 < n_tiles)
+      stage_transposed(&lds_kt[(t + 1) & 1][0][0], BN, 0,
+                       kp + (bh * L + kv0 + BN) * (int64_t)HD);
+    f32x4 s[2][4], dp[2][4];
+    __builtin_amdgcn_s_setprio(1);
+    score_tile<2>(aq, kp + (bh * L + kv0) * (int64_t)HD, ln, s);
+    score_tile<2>(ado, vp + (bh * L + kv0) * (int64_t)HD, ln, dp);
+    __builtin_amdgcn_s_setprio(0);
+    // redistribute P (both M-tiles), read A-fragments, then reuse for dP
+    bf16x8 pa[2][2];
 #pragma unroll
-  for (int mt = 0; mt < 2; ++mt) {
-    const int64_t kvbase = (bh * L + kv0w + mt * 16) * (int64_t)HD;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      ak[mt][ks] = load_frag(kp + kvbase + (int64_t)lr * HD + ks * 32 + lg * 8);
-      av[mt][ks] = load_frag(vp + kvbase + (int64_t)lr * HD + ks * 32 + lg * 8);
-    }
-  }
-  const uint16_t* mask_row = nullptr;
-  if (HAS_MASK) {
-    mask_row = mask + (((bh / mask_od) % mask_nb) * mask_q) * (int64_t)L;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        maskv[mt][r] = __bfloat162float(reinterpret_cast<const __hip_bfloat16*>(
-            mask_row)[kv0w + mt * 16 + lg * 4 + r]);
-  } else {
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) maskv[mt][r] = 0.f;
-  }
-
-  f32x4 dk_acc[2][4] = {}, dv_acc[2][4] = {};
-  const int n_tiles = L / BM;
-  for (int tq = 0; tq < n_tiles; ++tq) {
-    const int q0 = tq * BM;
-    {
-      const int qq = q0 + st_q0;
-      const int64_t row = (bh * L + qq) * (int64_t)HD;
-      float f0[8], f1[8];
-      load8(reinterpret_cast<const __hip_bfloat16*>(qp) + row + st_d0, f0);
-      load8(reinterpret_cast<const __hip_bfloat16*>(qp) + row + st_d0 + 8, f1);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int d0 = st_d0 + j;
-        const int d1 = st_d0 + 8 + j;
-        lds_qt[d0][st_q0 ^ ((d0 & 7) << 3)] = f32_to_bf16_bits(f0[j]);
-        lds_qt[d1][st_q0 ^ ((d1 & 7) << 3)] = f32_to_bf16_bits(f1[j]);
-      }
-    }
-    __syncthreads();
-    f32x4 st[2][4], dpt[2][4];
-#pragma unroll
-    for (int cq = 0; cq < 4; ++cq) {
-      const int qcol = q0 + cq * 16 + lr;
-      f32x4 a0 = {}, a1 = {}, d0 = {}, d1 = {};
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const bf16x8 bq =
-            load_frag(qp + (bh * L + qcol) * (int64_t)HD + ks * 32 + lg * 8);
-        const bf16x8 bdo =
-            load_frag(dop + (bh * L + qcol) * (int64_t)HD + ks * 32 + lg * 8);
-        a0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ak[0][ks], bq, a0, 0, 0, 0);
-        a1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ak[1][ks], bq, a1, 0, 0, 0);
-        d0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[0][ks], bdo, d0, 0, 0, 0);
-        d1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[1][ks], bdo, d1, 0, 0, 0);
-      }
-      st[0][cq] = a0;
-      st[1][cq] = a1;
-      dpt[0][cq] = d0;
-      dpt[1][cq] = d1;
+    for (int mtile = 0; mtile < 2; ++mtile) {
+      p_tile<HAS_BIAS, HAS_MASK>(s[mtile], bias_rows[mtile], mask_row,
+                                 lse_r[mtile], kv0, ln);
+      c_store(lds_t[ln.wid][mtile], s[mtile], ln);
     }
 #pragma unroll
-    for (int cq = 0; cq < 4; ++cq) {
-      const int qcol = q0 + cq * 16 + lr;
-      const float lse_c = lse[bh * L + qcol];
-      const float di_c = di[bh * L + qcol];
-      const uint16_t* brow =
-          HAS_BIAS ? bias + (((bh / bias_od) % bias_nb) * bias_q +
-                             (qcol % bias_q)) * (int64_t)L
-                   : nullptr;
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt) {
-        bool k8[8];
-        const int kvrow0 = kv0w + mt * 16 + lg * 4;
-        keep_bits8<DROP>(seed, (uint64_t)(bh * L + qcol), kvrow0 & ~7, pthresh,
-                         k8);
-        const int koff = kvrow0 & 7;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float sv = st[mt][cq][r];
-          if (HAS_BIAS)
-            sv += __bfloat162float(reinterpret_cast<const __hip_bfloat16*>(
-                brow)[kv0w + mt * 16 + lg * 4 + r]);
-          sv += maskv[mt][r];
-          const float pv = __expf(sv - lse_c);
-          float dpv = dpt[mt][cq][r];
-          const bool kp_ = !DROP || k8[koff + r];
-          if (DROP) dpv = kp_ ? dpv * pinv : 0.f;
-          st[mt][cq][r] = DROP ? (kp_ ? pv * pinv : 0.f) : pv;
-          dpt[mt][cq][r] = pv * (dpv - di_c);
-        }
-      }
-    }
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int cq = 0; cq < 4; ++cq)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          lds_t[wid][mt][lg * 4 + r][cq * 16 + lr] = f32_to_bf16_bits(st[mt][cq][r]);
-    bf16x8 pta[2][2];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
+    for (int mtile = 0; mtile < 2; ++mtile)
 #pragma unroll
       for (int ks2 = 0; ks2 < 2; ++ks2)
-        pta[mt][ks2] = load_frag(&lds_t[wid][mt][lr][ks2 * 32 + lg * 8]);
+        pa[mtile][ks2] = a_load(lds_t[ln.wid][mtile], ks2, ln);
 #pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int cq = 0; cq < 4; ++cq)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          lds_t[wid][mt][lg * 4 + r][cq * 16 + lr] =
-              f32_to_bf16_bits(dpt[mt][cq][r]);
+    for (int mtile = 0; mtile < 2; ++mtile)
+      c_store(lds_t[ln.wid][mtile], dp[mtile], ln);
 #pragma unroll
     for (int ks2 = 0; ks2 < 2; ++ks2) {
-      bf16x8 dsta[2];
+      const int kv = kv0 + ks2 * 32 + ln.lg * 8;
+      bf16x8 dsa[2];
 #pragma unroll
-      for (int mt = 0; mt < 2; ++mt)
-        dsta[mt] = load_frag(&lds_t[wid][mt][lr][ks2 * 32 + lg * 8]);
-#pragma unroll
-      for (int cb = 0; cb < 4; ++cb) {
-        const int d = cb * 16 + lr;
-        const int qx_dot = (q0 + ks2 * 32 + lg * 8) ^ ((d & 7) << 3);
-        const int qx_q = (ks2 * 32 + lg * 8) ^ ((d & 7) << 3);
-        const bf16x8 bdo = load_frag(&lds_dot[d][qx_dot]);
-        const bf16x8 bqf = load_frag(&lds_qt[d][qx_q]);
-        dv_acc[0][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pta[0][ks2], bdo,
-                                                               dv_acc[0][cb], 0, 0, 0);
-        dv_acc[1][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pta[1][ks2], bdo,
-                                                               dv_acc[1][cb], 0, 0, 0);
-        dk_acc[0][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dsta[0], bqf,
-                                                               dk_acc[0][cb], 0, 0, 0);
-        dk_acc[1][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dsta[1], bqf,
-                                                               dk_acc[1][cb], 0, 0, 0);
+      for (int mtile = 0; mtile < 2; ++mtile) {
+        const int64_t row = bh * L + ln.row0 + mtile * 16 + ln.lr;
+        float dsf[8];
+        ds_frag<DROP>(pa[mtile][ks2], a_load(lds_t[ln.wid][mtile], ks2, ln),
+                      di_row[mtile], dr, row, kv, dsa[mtile], dsf);
+        store_ds(ds_out, row, L, kv, dsa[mtile]);
       }
+      mma_staged<2>(dsa, &lds_kt[t & 1][0][0], BN, ks2 * 32, ln, dq_acc);
     }
+    // publish tile t+1's staging; reads of buffer t&1 are also done, so
+    // its restage at t+2 (after the next barrier) is safe
     __syncthreads();
   }
 #pragma unroll
-  for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int kv = kv0w + mt * 16 + lg * 4 + r;
-#pragma unroll
-      for (int cb = 0; cb < 4; ++cb) {
-        dk[(bh * L + kv) * (int64_t)HD + cb * 16 + lr] =
-            f32_to_bf16_bits(dk_acc[mt][cb][r]);
-        dv[(bh * L + kv) * (int64_t)HD + cb * 16 + lr] =
-            f32_to_bf16_bits(dv_acc[mt][cb][r]);
-      }
-    }
+  for (int mtile = 0; mtile < 2; ++mtile)
+    store_c_tile(dq, bh * L + ln.row0 + mtile * 16, dq_acc[mtile], ln);
 }
 
-template <bool HAS_BIAS, bool HAS_MASK, bool DROP, int LMAX>
+// ---- dK / dV: one wave owns 16 kv rows and walks the q tiles ---------------
+
+// additive mask of the 4 kv rows kv_first + [0..4) (constant over q)
+template <bool HAS_MASK>
+__device__ __forceinline__ void load_maskv(const Src& mask, int64_t bh,
+                                           int kv_first, int L,
+                                           float (&maskv)[4]) {
+  const uint16_t* mask_row = mask_row_of<HAS_MASK>(mask, bh, L);
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+    maskv[r] = HAS_MASK ? bf16_at(mask_row, kv_first + r) : 0.f;
+}
+
+// On the transposed 16 kv x 64 q C tiles of q tile q0 (lane: kv rows
+// kv_first + [0..4), q column q0 + cq*16 + lr):
+//   P^T = exp(S^T + bias + mask - lse[q]);
+//   st <- dropped P^T (dV's operand), dpt <- dS^T = P^T o (drop(dP^T) - Di[q])
+template <bool HAS_BIAS, bool DROP>
+__device__ __forceinline__ void pt_dst_tile(f32x4 (&st)[4], f32x4 (&dpt)[4],
+                                            const float* lse, const float* di,
+                                            const Src& bias,
+                                            const float (&maskv)[4], int64_t bh,
+                                            int q0, int kv_first, int L,
+                                            const Drop& dr, const Lane& ln) {
+#pragma unroll
+  for (int cq = 0; cq < 4; ++cq) {
+    const int qcol = q0 + cq * 16 + ln.lr;
+    const float lse_c = lse[bh * L + qcol];
+    const float di_c = di[bh * L + qcol];
+    const uint16_t* brow = HAS_BIAS ? bias.row(bh, qcol, L) : nullptr;
+    bool keep[4] = {true, true, true, true};
+    if (DROP) {
+      // this lane's 4 kv rows live in one 8-block of the keep definition
+      bool k8[8];
+      const int blk = kv_first & ~7;
+      keep16x8(dr.seed, (uint64_t)(bh * L + qcol), blk, dr.pthresh, k8);
+      const int off = kv_first - blk;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) keep[r] = k8[off + r];
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float sv = add_bias_mask<HAS_BIAS, false>(st[cq][r], brow, nullptr,
+                                                      kv_first + r) +
+                       maskv[r];
+      const float pv = p_from_lse(sv, lse_c);
+      float dpv = dpt[cq][r];
+      if (DROP) dpv = keep[r] ? dpv * dr.pinv : 0.f;
+      st[cq][r] = DROP ? (keep[r] ? pv * dr.pinv : 0.f) : pv;
+      dpt[cq][r] = pv * (dpv - di_c);
+    }
+  }
+}
+
+// dkv for L <= LRES.  Both transposed operands (Q^T, dO^T) are staged per
+// q-tile (8 KB each), ping-pong, rather than keeping dO^T L-resident
+// (64 KB): the resident version held the block at 80 KB LDS -> 2 blocks/CU,
+// and PMC showed the kernel parked on waits — occupancy was the binding
+// constraint.  The P^T/dS^T redistribute buffer is shared sequentially
+// (wave-local ordering).
+template <bool HAS_BIAS, bool HAS_MASK, bool DROP>
 __global__ __launch_bounds__(256, 3) void flash_bwd_dkv_qres_kernel(
     uint16_t* __restrict__ dk, uint16_t* __restrict__ dv,
     const uint16_t* __restrict__ dop, const uint16_t* __restrict__ qp,
     const uint16_t* __restrict__ kp, const uint16_t* __restrict__ vp,
-    const float* __restrict__ lse, const float* __restrict__ di,
-    const uint16_t* __restrict__ bias, int64_t bias_nb, int bias_q, int64_t bias_od,
-    const uint16_t* __restrict__ mask, int64_t mask_nb, int mask_q, int64_t mask_od,
-    int L, float pinv, uint32_t pthresh, uint64_t seed) {
-  const int kt = blockIdx.x;
+    const float* __restrict__ lse, const float* __restrict__ di, Src bias,
+    Src mask, int L, Drop dr) {
+  const Lane ln = lane_coords(16);
   const int64_t bh = blockIdx.y;
-  const int wid = threadIdx.x >> 6;
-  const int lane = threadIdx.x & 63;
-  const int lg = lane >> 4;
-  const int lr = lane & 15;
-  const int kv0w = kt * BN + wid * 16;
-  const int64_t kvbase = (bh * L + kv0w) * HD;
+  const int64_t row0 = bh * L + ln.row0;   // this wave's first kv row
 
-  // Both transposed operands (Q^T, dO^T) are staged per q-tile (8 KB
-  // each) rather than keeping dO^T L-resident (64 KB): the resident
-  // version held the block at 80 KB LDS -> 2 blocks/CU, and PMC showed
-  // the kernel parked on waits — occupancy was the binding constraint.
   __shared__ __attribute__((aligned(16))) uint16_t lds_t[4][16][BN];
   __shared__ __attribute__((aligned(16))) uint16_t lds_dot[2][HD][BM];
   __shared__ __attribute__((aligned(16))) uint16_t lds_qt[2][HD][BM];
-  const int st_q0 = (int)threadIdx.x >> 2;
-  const int st_d0 = ((int)threadIdx.x & 3) * 16;
 
-  bf16x8 ak[2], av[2];
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks) {
-    ak[ks] = load_frag(kp + kvbase + (int64_t)lr * HD + ks * 32 + lg * 8);
-    av[ks] = load_frag(vp + kvbase + (int64_t)lr * HD + ks * 32 + lg * 8);
-  }
-  const uint16_t* mask_row = nullptr;
-  if (HAS_MASK)
-    mask_row = mask + (((bh / mask_od) % mask_nb) * mask_q) * (int64_t)L;
+  bf16x8 ak[1][2], av[1][2];
+  load_a(kp, row0, ln, ak[0]);
+  load_a(vp, row0, ln, av[0]);
   float maskv[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-    maskv[r] = HAS_MASK
-                   ? __bfloat162float(reinterpret_cast<const __hip_bfloat16*>(
-                         mask_row)[kv0w + lg * 4 + r])
-                   : 0.f;
+  load_maskv<HAS_MASK>(mask, bh, ln.row0 + ln.lg * 4, L, maskv);
 
-  f32x4 dk_acc[4] = {}, dv_acc[4] = {};
+  f32x4 dk_acc[1][4] = {}, dv_acc[1][4] = {};
   const int n_tiles = L / BM;
   // (T14 prefetch tried and reverted here too: 845 -> 918 us at the
-  // 3->2 blocks/CU occupancy cost; see the dq kernel's note.)
+  // 3->2 blocks/CU occupancy cost; see the dq_k32 kernel's note.)
   // ping-pong staging of Q^T/dO^T: tile tq+1 stages into the other
   // buffer while tile tq computes, one barrier per iteration
   auto stage_q = [&](int tile) {
-    const int qq = tile * BM + st_q0;
-    const int64_t row = (bh * L + qq) * (int64_t)HD;
-    uint16_t* bq = &lds_qt[tile & 1][0][0];
-    uint16_t* bd = &lds_dot[tile & 1][0][0];
-    float f0[8], f1[8], g0[8], g1[8];
-    load8(reinterpret_cast<const __hip_bfloat16*>(qp) + row + st_d0, f0);
-    load8(reinterpret_cast<const __hip_bfloat16*>(qp) + row + st_d0 + 8, f1);
-    load8(reinterpret_cast<const __hip_bfloat16*>(dop) + row + st_d0, g0);
-    load8(reinterpret_cast<const __hip_bfloat16*>(dop) + row + st_d0 + 8, g1);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int d0 = st_d0 + j;
-      const int d1 = st_d0 + 8 + j;
-      bq[d0 * BM + (st_q0 ^ ((d0 & 7) << 3))] = f32_to_bf16_bits(f0[j]);
-      bq[d1 * BM + (st_q0 ^ ((d1 & 7) << 3))] = f32_to_bf16_bits(f1[j]);
-      bd[d0 * BM + (st_q0 ^ ((d0 & 7) << 3))] = f32_to_bf16_bits(g0[j]);
-      bd[d1 * BM + (st_q0 ^ ((d1 & 7) << 3))] = f32_to_bf16_bits(g1[j]);
-    }
+    const int64_t off = (bh * L + tile * BM) * (int64_t)HD;
+    stage_transposed(&lds_qt[tile & 1][0][0], BM, 0, qp + off);
+    stage_transposed(&lds_dot[tile & 1][0][0], BM, 0, dop + off);
   };
   stage_q(0);
   __syncthreads();
   for (int tq = 0; tq < n_tiles; ++tq) {
     const int q0 = tq * BM;
     if (tq + 1 < n_tiles) stage_q(tq + 1);
-    f32x4 st[4], dpt[4];
-#pragma unroll
-    for (int cq = 0; cq < 4; ++cq) {
-      const int qcol = q0 + cq * 16 + lr;
-      f32x4 acc = {}, accd = {};
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const bf16x8 bq =
-            load_frag(qp + (bh * L + qcol) * (int64_t)HD + ks * 32 + lg * 8);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ak[ks], bq, acc, 0, 0, 0);
-        const bf16x8 bdo =
-            load_frag(dop + (bh * L + qcol) * (int64_t)HD + ks * 32 + lg * 8);
-        accd = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[ks], bdo, accd, 0, 0, 0);
-      }
-      st[cq] = acc;
-      dpt[cq] = accd;
-    }
-#pragma unroll
-    for (int cq = 0; cq < 4; ++cq) {
-      const int qcol = q0 + cq * 16 + lr;
-      const float lse_c = lse[bh * L + qcol];
-      const float di_c = di[bh * L + qcol];
-      const uint16_t* brow =
-          HAS_BIAS ? bias + (((bh / bias_od) % bias_nb) * bias_q +
-                             (qcol % bias_q)) * (int64_t)L
-                   : nullptr;
-      bool keep[4] = {true, true, true, true};
-      if (DROP) {
-        bool k8[8];
-        const int blk = (kv0w + lg * 4) & ~7;
-        keep16x8(seed, (uint64_t)(bh * L + qcol), blk, pthresh, k8);
-        const int off = (kv0w + lg * 4) - blk;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) keep[r] = k8[off + r];
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float sv = st[cq][r];
-        if (HAS_BIAS)
-          sv += __bfloat162float(reinterpret_cast<const __hip_bfloat16*>(
-              brow)[kv0w + lg * 4 + r]);
-        sv += maskv[r];
-        const float pv = __expf(sv - lse_c);
-        float dpv = dpt[cq][r];
-        if (DROP) dpv = keep[r] ? dpv * pinv : 0.f;
-        st[cq][r] = DROP ? (keep[r] ? pv * pinv : 0.f) : pv;
-        dpt[cq][r] = pv * (dpv - di_c);
-      }
-    }
+    f32x4 st[1][4], dpt[1][4];
+    score_tile<1>(ak, qp + (bh * L + q0) * (int64_t)HD, ln, st);
+    score_tile<1>(av, dop + (bh * L + q0) * (int64_t)HD, ln, dpt);
+    pt_dst_tile<HAS_BIAS, DROP>(st[0], dpt[0], lse, di, bias, maskv, bh, q0,
+                                ln.row0 + ln.lg * 4, L, dr, ln);
     // redistribute P^T first (shared buffer, wave-local ordering), read
     // both A-fragments into registers, then reuse the buffer for dS^T
+    c_store(lds_t[ln.wid], st[0], ln);
+    bf16x8 pta[2][1];
 #pragma unroll
-    for (int cq = 0; cq < 4; ++cq)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        lds_t[wid][lg * 4 + r][cq * 16 + lr] = f32_to_bf16_bits(st[cq][r]);
-    bf16x8 pta[2];
-#pragma unroll
-    for (int ks2 = 0; ks2 < 2; ++ks2)
-      pta[ks2] = load_frag(&lds_t[wid][lr][ks2 * 32 + lg * 8]);
-#pragma unroll
-    for (int cq = 0; cq < 4; ++cq)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        lds_t[wid][lg * 4 + r][cq * 16 + lr] = f32_to_bf16_bits(dpt[cq][r]);
+    for (int ks2 = 0; ks2 < 2; ++ks2) pta[ks2][0] = a_load(lds_t[ln.wid], ks2, ln);
+    c_store(lds_t[ln.wid], dpt[0], ln);
 #pragma unroll
     for (int ks2 = 0; ks2 < 2; ++ks2) {
-      const bf16x8 dsta = load_frag(&lds_t[wid][lr][ks2 * 32 + lg * 8]);
-#pragma unroll
-      for (int cb = 0; cb < 4; ++cb) {
-        const int d = cb * 16 + lr;
-        const int qx = (ks2 * 32 + lg * 8) ^ ((d & 7) << 3);  // tile-local
-        const bf16x8 bdo = load_frag(&lds_dot[tq & 1][d][qx]);
-        const bf16x8 bqf = load_frag(&lds_qt[tq & 1][d][qx]);
-        dv_acc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pta[ks2], bdo,
-                                                            dv_acc[cb], 0, 0, 0);
-        dk_acc[cb] =
-            __builtin_amdgcn_mfma_f32_16x16x32_bf16(dsta, bqf, dk_acc[cb], 0, 0, 0);
-      }
+      const bf16x8 dsta[1] = {a_load(lds_t[ln.wid], ks2, ln)};
+      mma_staged<1>(pta[ks2], &lds_dot[tq & 1][0][0], BM, ks2 * 32, ln, dv_acc);
+      mma_staged<1>(dsta, &lds_qt[tq & 1][0][0], BM, ks2 * 32, ln, dk_acc);
     }
     __syncthreads();
   }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int kv = kv0w + lg * 4 + r;
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb) {
-      dk[(bh * L + kv) * (int64_t)HD + cb * 16 + lr] =
-          f32_to_bf16_bits(dk_acc[cb][r]);
-      dv[(bh * L + kv) * (int64_t)HD + cb * 16 + lr] =
-          f32_to_bf16_bits(dv_acc[cb][r]);
-    }
-  }
+  store_c_tile(dk, row0, dk_acc[0], ln);
+  store_c_tile(dv, row0, dv_acc[0], ln);
 }
 
+// dkv for L > LRES: Q^T and dO^T staged per q tile between two barriers.
+// The tile loop keeps its statements written out and the kernel its loose
+// arguments, as in flash_bwd_dq_kernel and for the same reason: built from
+// score_tile, pt_dst_tile, c_store / a_load and mma_staged it took 192-196
+// VGPRs without dropout where this text takes 148-152.  Lane, Src::row,
+// load_maskv, swz and store_c_tile are shared.
 template <bool HAS_BIAS, bool HAS_MASK, bool DROP>
 __global__ __launch_bounds__(256) void flash_bwd_dkv_kernel(
     uint16_t* __restrict__ dk, uint16_t* __restrict__ dv,
@@ -1522,13 +1107,12 @@ __global__ __launch_bounds__(256) void flash_bwd_dkv_kernel(
     const uint16_t* __restrict__ bias, int64_t bias_nb, int bias_q, int64_t bias_od,
     const uint16_t* __restrict__ mask, int64_t mask_nb, int mask_q, int64_t mask_od,
     int L, float pinv, uint32_t pthresh, uint64_t seed) {
-  const int kt = blockIdx.x;
+  const Lane ln = lane_coords(16);
   const int64_t bh = blockIdx.y;
-  const int wid = threadIdx.x >> 6;
-  const int lane = threadIdx.x & 63;
-  const int lg = lane >> 4;
-  const int lr = lane & 15;
-  const int kv0w = kt * BN + wid * 16;   // this wave's first kv row
+  const int wid = ln.wid, lg = ln.lg, lr = ln.lr;
+  const int kv0w = ln.row0;   // this wave's first kv row
+  const Src bias_src{bias, bias_nb, bias_q, bias_od};
+  const Src mask_src{mask, mask_nb, mask_q, mask_od};
   const int64_t kvbase = (bh * L + kv0w) * HD;
 
   __shared__ __attribute__((aligned(16))) uint16_t lds_t[4][2][16][BN];
@@ -1544,16 +1128,8 @@ __global__ __launch_bounds__(256) void flash_bwd_dkv_kernel(
     ak[ks] = load_frag(kp + kvbase + (int64_t)lr * HD + ks * 32 + lg * 8);
     av[ks] = load_frag(vp + kvbase + (int64_t)lr * HD + ks * 32 + lg * 8);
   }
-  const uint16_t* mask_row = nullptr;
-  if (HAS_MASK)
-    mask_row = mask + (((bh / mask_od) % mask_nb) * mask_q) * (int64_t)L;
   float maskv[4];   // additive mask for this wave's kv rows (constant over q)
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-    maskv[r] = HAS_MASK
-                   ? __bfloat162float(reinterpret_cast<const __hip_bfloat16*>(
-                         mask_row)[kv0w + lg * 4 + r])
-                   : 0.f;
+  load_maskv<HAS_MASK>(mask_src, bh, kv0w + lg * 4, L, maskv);
 
   f32x4 dk_acc[4] = {}, dv_acc[4] = {};
   const int n_tiles = L / BM;
@@ -1568,8 +1144,8 @@ __global__ __launch_bounds__(256) void flash_bwd_dkv_kernel(
       for (int j = 0; j < 8; ++j) {
         const int d0 = st_d0 + j;
         const int d1 = st_d0 + 8 + j;
-        lds_dot[d0][st_q ^ ((d0 & 7) << 3)] = f32_to_bf16_bits(f0[j]);
-        lds_dot[d1][st_q ^ ((d1 & 7) << 3)] = f32_to_bf16_bits(f1[j]);
+        lds_dot[d0][swz(d0, st_q)] = f32_to_bf16_bits(f0[j]);
+        lds_dot[d1][swz(d1, st_q)] = f32_to_bf16_bits(f1[j]);
       }
       load8(reinterpret_cast<const __hip_bfloat16*>(qp) + row + st_d0, f0);
       load8(reinterpret_cast<const __hip_bfloat16*>(qp) + row + st_d0 + 8, f1);
@@ -1577,8 +1153,8 @@ __global__ __launch_bounds__(256) void flash_bwd_dkv_kernel(
       for (int j = 0; j < 8; ++j) {
         const int d0 = st_d0 + j;
         const int d1 = st_d0 + 8 + j;
-        lds_qt[d0][st_q ^ ((d0 & 7) << 3)] = f32_to_bf16_bits(f0[j]);
-        lds_qt[d1][st_q ^ ((d1 & 7) << 3)] = f32_to_bf16_bits(f1[j]);
+        lds_qt[d0][swz(d0, st_q)] = f32_to_bf16_bits(f0[j]);
+        lds_qt[d1][swz(d1, st_q)] = f32_to_bf16_bits(f1[j]);
       }
     }
     __syncthreads();
@@ -1605,10 +1181,7 @@ __global__ __launch_bounds__(256) void flash_bwd_dkv_kernel(
       const int qcol = q0 + cq * 16 + lr;
       const float lse_c = lse[bh * L + qcol];
       const float di_c = di[bh * L + qcol];
-      const uint16_t* brow =
-          HAS_BIAS ? bias + (((bh / bias_od) % bias_nb) * bias_q +
-                             (qcol % bias_q)) * (int64_t)L
-                   : nullptr;
+      const uint16_t* brow = HAS_BIAS ? bias_src.row(bh, qcol, L) : nullptr;
       bool keep[4] = {true, true, true, true};
       if (DROP) {
         // this lane's kv rows kv0w + lg*4 + [0..4) live in one 8-block
@@ -1648,7 +1221,7 @@ __global__ __launch_bounds__(256) void flash_bwd_dkv_kernel(
 #pragma unroll
       for (int cb = 0; cb < 4; ++cb) {
         const int d = cb * 16 + lr;
-        const int qx = (ks2 * 32 + lg * 8) ^ ((d & 7) << 3);
+        const int qx = swz(d, ks2 * 32 + lg * 8);
         const bf16x8 bdo = load_frag(&lds_dot[d][qx]);
         const bf16x8 bqf = load_frag(&lds_qt[d][qx]);
         dv_acc[cb] =
@@ -1659,17 +1232,8 @@ __global__ __launch_bounds__(256) void flash_bwd_dkv_kernel(
     }
     __syncthreads();
   }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int kv = kv0w + lg * 4 + r;
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb) {
-      dk[(bh * L + kv) * (int64_t)HD + cb * 16 + lr] =
-          f32_to_bf16_bits(dk_acc[cb][r]);
-      dv[(bh * L + kv) * (int64_t)HD + cb * 16 + lr] =
-          f32_to_bf16_bits(dv_acc[cb][r]);
-    }
-  }
+  store_c_tile(dk, bh * L + kv0w, dk_acc, ln);
+  store_c_tile(dv, bh * L + kv0w, dv_acc, ln);
 }
 
 }  // namespace
@@ -1679,30 +1243,28 @@ std::vector<at::Tensor> flash_attn_backward(
     at::Tensor lse, std::optional<at::Tensor> bias, int64_t bias_outer_div,
     bool bias_needs_grad, std::optional<at::Tensor> mask, int64_t mask_outer_div,
     double dropout_p, bool dropped, int64_t seed_in) {
-  TORCH_CHECK(d_out.is_cuda() && d_out.is_contiguous() && q.is_contiguous() &&
-                  k.is_contiguous() && v.is_contiguous() && o.is_contiguous(),
-              "flash_attn_backward: tensors must be contiguous CUDA");
+  const int L = check_inputs(
+      "flash_attn_backward",
+      {{"q", &q}, {"k", &k}, {"v", &v}, {"o", &o}, {"d_out", &d_out}});
   const int64_t BH = q.size(0);
-  const int L = (int)q.size(1);
-  const SrcDesc bd = describe(bias, bias_outer_div, L, "bias");
-  const SrcDesc md = describe(mask, mask_outer_div, L, "mask");
+  TORCH_CHECK(lse.is_cuda() && lse.is_contiguous() &&
+                  lse.scalar_type() == at::kFloat && lse.dim() == 2 &&
+                  lse.size(0) == BH && lse.size(1) == L,
+              "flash_attn_backward: lse must be contiguous fp32 (", BH, ", ", L,
+              "), got ", lse.scalar_type(), " ", lse.sizes());
+  const Src bd = describe(bias, bias_outer_div, L, "bias");
+  const Src md = describe(mask, mask_outer_div, L, "mask");
+  TORCH_CHECK(md.q == 1,
+              "flash_attn_backward: mask must broadcast over q, got q = ", md.q);
 
   const bool drop = dropped && dropout_p > 0.0;
-  float pinv = 1.f;
-  uint32_t pthresh = 0;
-  if (drop) {
-    const double pc = std::min(dropout_p, 0.999999);
-    pinv = (float)(1.0 / (1.0 - pc));
-    pthresh = keep16_threshold(pc);
-  }
-  const uint64_t seed = (uint64_t)seed_in;
+  const Drop dr = make_drop(drop, dropout_p, (uint64_t)seed_in);
 
   auto stream = at::cuda::getCurrentCUDAStream();
   auto di = at::empty({BH, (int64_t)L}, q.options().dtype(at::kFloat));
   const int64_t n_rows = BH * L;
   flash_dot_do_o_kernel<<<unicore_grid((n_rows + 31) / 32), 256, 0, stream>>>(
-      di.data_ptr<float>(), reinterpret_cast<const uint16_t*>(d_out.data_ptr()),
-      reinterpret_cast<const uint16_t*>(o.data_ptr()), n_rows);
+      di.data_ptr<float>(), bits(d_out), bits(o), n_rows);
 
   auto dq = at::empty_like(q);
   auto dk = at::empty_like(k);
@@ -1730,86 +1292,39 @@ std::vector<at::Tensor> flash_attn_backward(
       ds = at::empty({BH, (int64_t)L, (int64_t)L}, q.options());
   }
   float* dbias_ptr = dbias.defined() ? dbias.data_ptr<float>() : nullptr;
+  uint16_t* ds_ptr = ds.defined() ? bits_mut(ds) : nullptr;
   const dim3 grid(L / BM, BH);
+  const auto common = std::make_tuple(
+      bits(d_out), bits(q), bits(k), bits(v),
+      static_cast<const float*>(lse.data_ptr<float>()),
+      static_cast<const float*>(di.data_ptr<float>()), bd, md, L, dr);
+  // the two tiled kernels take the same values as loose arguments
+  const auto loose = std::make_tuple(
+      bits(d_out), bits(q), bits(k), bits(v),
+      static_cast<const float*>(lse.data_ptr<float>()),
+      static_cast<const float*>(di.data_ptr<float>()), bd.ptr, bd.nb, bd.q,
+      bd.od, md.ptr, md.nb, md.q, md.od, L, dr.pinv, dr.pthresh, dr.seed);
 
-  auto launch_all = [&](auto hb, auto hm, auto dr) {
+  dispatch_flags(bd.ptr, md.ptr, drop, [&](auto hb, auto hm, auto dt) {
     constexpr bool HB = decltype(hb)::value;
     constexpr bool HM = decltype(hm)::value;
-    constexpr bool DR = decltype(dr)::value;
-    if (L <= 512 && L % 128 == 0)
-      flash_bwd_dq_k32_kernel<HB, HM, DR, 512>
-          <<<dim3(L / 128, BH), 256, 0, stream>>>(
-              reinterpret_cast<uint16_t*>(dq.data_ptr()),
-              ds.defined() ? reinterpret_cast<uint16_t*>(ds.data_ptr())
-                           : nullptr,
-              reinterpret_cast<const uint16_t*>(d_out.data_ptr()),
-              reinterpret_cast<const uint16_t*>(q.data_ptr()),
-              reinterpret_cast<const uint16_t*>(k.data_ptr()),
-              reinterpret_cast<const uint16_t*>(v.data_ptr()),
-              lse.data_ptr<float>(), di.data_ptr<float>(),
-              reinterpret_cast<const uint16_t*>(bd.ptr), bd.nb, bd.q, bd.od,
-              reinterpret_cast<const uint16_t*>(md.ptr), md.nb, md.q, md.od, L,
-              pinv, pthresh, seed);
-    else if (L <= 512)
-      flash_bwd_dq_kres_kernel<HB, HM, DR, 512><<<grid, 256, 0, stream>>>(
-          reinterpret_cast<uint16_t*>(dq.data_ptr()),
-          ds.defined() ? reinterpret_cast<uint16_t*>(ds.data_ptr()) : nullptr,
-          reinterpret_cast<const uint16_t*>(d_out.data_ptr()),
-          reinterpret_cast<const uint16_t*>(q.data_ptr()),
-          reinterpret_cast<const uint16_t*>(k.data_ptr()),
-          reinterpret_cast<const uint16_t*>(v.data_ptr()), lse.data_ptr<float>(),
-          di.data_ptr<float>(), reinterpret_cast<const uint16_t*>(bd.ptr), bd.nb,
-          bd.q, bd.od, reinterpret_cast<const uint16_t*>(md.ptr), md.nb, md.q,
-          md.od, L, pinv, pthresh, seed);
+    constexpr bool DR = decltype(dt)::value;
+    if (L <= LRES && L % 128 == 0)
+      launch(flash_bwd_dq_k32_kernel<HB, HM, DR>, dim3(L / 128, BH), stream,
+             common, bits_mut(dq), ds_ptr);
+    else if (L <= LRES)
+      launch(flash_bwd_dq_kernel<HB, HM, DR, true>, grid, stream, loose,
+             bits_mut(dq), ds_ptr, NoDbiasAcc{});
     else
-      flash_bwd_dq_kernel<HB, HM, DR><<<grid, 256, 0, stream>>>(
-        reinterpret_cast<uint16_t*>(dq.data_ptr()),
-        ds.defined() ? reinterpret_cast<uint16_t*>(ds.data_ptr()) : nullptr,
-        dbias_ptr,
-        reinterpret_cast<const uint16_t*>(d_out.data_ptr()),
-        reinterpret_cast<const uint16_t*>(q.data_ptr()),
-        reinterpret_cast<const uint16_t*>(k.data_ptr()),
-        reinterpret_cast<const uint16_t*>(v.data_ptr()), lse.data_ptr<float>(),
-        di.data_ptr<float>(), reinterpret_cast<const uint16_t*>(bd.ptr), bd.nb,
-        bd.q, bd.od, reinterpret_cast<const uint16_t*>(md.ptr), md.nb, md.q,
-        md.od, L, pinv, pthresh, seed);
-    if (L <= 512)
-      flash_bwd_dkv_qres_kernel<HB, HM, DR, 512><<<grid, 256, 0, stream>>>(
-          reinterpret_cast<uint16_t*>(dk.data_ptr()),
-          reinterpret_cast<uint16_t*>(dv.data_ptr()),
-          reinterpret_cast<const uint16_t*>(d_out.data_ptr()),
-          reinterpret_cast<const uint16_t*>(q.data_ptr()),
-          reinterpret_cast<const uint16_t*>(k.data_ptr()),
-          reinterpret_cast<const uint16_t*>(v.data_ptr()), lse.data_ptr<float>(),
-          di.data_ptr<float>(), reinterpret_cast<const uint16_t*>(bd.ptr), bd.nb,
-          bd.q, bd.od, reinterpret_cast<const uint16_t*>(md.ptr), md.nb, md.q,
-          md.od, L, pinv, pthresh, seed);
+      launch(flash_bwd_dq_kernel<HB, HM, DR, false>, grid, stream, loose,
+             bits_mut(dq), ds_ptr, dbias_ptr);
+    if (L <= LRES)
+      launch(flash_bwd_dkv_qres_kernel<HB, HM, DR>, grid, stream, common,
+             bits_mut(dk), bits_mut(dv));
     else
-      flash_bwd_dkv_kernel<HB, HM, DR><<<grid, 256, 0, stream>>>(
-        reinterpret_cast<uint16_t*>(dk.data_ptr()),
-        reinterpret_cast<uint16_t*>(dv.data_ptr()),
-        reinterpret_cast<const uint16_t*>(d_out.data_ptr()),
-        reinterpret_cast<const uint16_t*>(q.data_ptr()),
-        reinterpret_cast<const uint16_t*>(k.data_ptr()),
-        reinterpret_cast<const uint16_t*>(v.data_ptr()), lse.data_ptr<float>(),
-        di.data_ptr<float>(), reinterpret_cast<const uint16_t*>(bd.ptr), bd.nb,
-        bd.q, bd.od, reinterpret_cast<const uint16_t*>(md.ptr), md.nb, md.q,
-        md.od, L, pinv, pthresh, seed);
-  };
-  auto pick = [&](auto hb, auto hm) {
-    if (drop)
-      launch_all(hb, hm, std::true_type{});
-    else
-      launch_all(hb, hm, std::false_type{});
-  };
-  if (bd.ptr && md.ptr)
-    pick(std::true_type{}, std::true_type{});
-  else if (bd.ptr)
-    pick(std::true_type{}, std::false_type{});
-  else if (md.ptr)
-    pick(std::false_type{}, std::true_type{});
-  else
-    pick(std::false_type{}, std::false_type{});
+      launch(flash_bwd_dkv_kernel<HB, HM, DR>, grid, stream, loose,
+             bits_mut(dk), bits_mut(dv));
+  });
 
   C10_CUDA_KERNEL_LAUNCH_CHECK();
   if (dbias.defined()) return {dq, dk, dv, dbias};

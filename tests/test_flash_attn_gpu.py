@@ -41,6 +41,32 @@ def test_flash_fwd_plain(L):
 
 
 @requires_gpu
+@pytest.mark.parametrize("with_bias_mask", [False, True])
+def test_flash_fwd_tiled(with_bias_mask):
+    """L = 576 (9 tiles) is the smallest L > 512: the tiled forward, which
+    stages V^T per tile, is what every longer no_grad forward runs."""
+    from unicore_amd import ops
+
+    torch.manual_seed(12)
+    B, H, L = 2, 3, 576
+    q = torch.randn(B * H, L, 64, device="cuda", dtype=torch.bfloat16) * 0.2
+    k, v = torch.randn_like(q), torch.randn_like(q)
+    bias = mask = bias4 = mask4 = None
+    if with_bias_mask:
+        bias = torch.randn(H, L, L, device="cuda", dtype=torch.bfloat16)
+        mask = torch.zeros(B, 1, L, device="cuda", dtype=torch.bfloat16)
+        mask[:, :, -17:] = float(torch.finfo(torch.float16).min)
+        bias4, mask4 = bias.unsqueeze(0), mask.view(B, 1, 1, L)
+    o, lse, seed = ops.flash_attn_fwd(q, k, v, bias, 1, mask, H, 0.0, True)
+    ref, s = _ref_attn(q.view(B, H, L, 64), k.view(B, H, L, 64),
+                       v.view(B, H, L, 64), bias4, mask4)
+    diff = (o.view(B, H, L, 64).float() - ref).abs().max().item()
+    assert diff < 2e-2, diff
+    ref_lse = torch.logsumexp(s, dim=-1)
+    assert (lse.view(B, H, L) - ref_lse).abs().max().item() < 1e-3
+
+
+@requires_gpu
 def test_flash_fwd_bias_mask():
     from unicore_amd import ops
 
@@ -87,7 +113,7 @@ def test_flash_fwd_dropout_stats_and_determinism():
 
 
 @requires_gpu
-@pytest.mark.parametrize("L", [64, 256])
+@pytest.mark.parametrize("L", [64, 192, 256, 576])
 def test_flash_bwd_parity_no_dropout(L):
     from unicore_amd import ops
 
@@ -168,6 +194,141 @@ def test_flash_bwd_dropout_identity_v():
     cmp(dq, qr.grad, 0.06, "dq")
     cmp(dk, kr.grad, 0.06, "dk")
     cmp(dv, vr.grad, 0.06, "dv")
+
+
+def _identity_block_v(BH, L, c):
+    """V whose rows 64c .. 64c+63 are the identity and all others zero, so
+    that O = dropout(P) V is columns 64c .. 64c+63 of dropout(P)."""
+    v = torch.zeros(BH, L, 64, device="cuda", dtype=torch.bfloat16)
+    v[:, 64 * c:64 * (c + 1), :] = torch.eye(64, device="cuda",
+                                             dtype=torch.bfloat16)
+    return v
+
+
+@requires_gpu
+@pytest.mark.parametrize("L,with_bias",
+                         [(192, False), (192, True), (256, True), (576, True)])
+def test_flash_bwd_dropout_explicit_mask(L, with_bias):
+    """The identity-V trick beyond one tile.  The keep bits depend on
+    (seed, row, kv) only, so L / 64 forwards from the same generator state,
+    each with one 64-row identity block in V, read out the whole keep mask;
+    forward and backward with a random V and that seed are then compared
+    with an explicit-mask fp32 reference.  L = 192 runs dq_kres + dkv_qres,
+    256 dq_k32 + dkv_qres, 576 the tiled forward, dq and dkv."""
+    from unicore_amd import ops
+
+    torch.manual_seed(5)
+    B, H, p = 2, 3, 0.3
+    BH = B * H
+    q = torch.randn(BH, L, 64, device="cuda", dtype=torch.bfloat16) * 0.2
+    k, v = torch.randn_like(q), torch.randn_like(q)
+    bias = None
+    if with_bias:
+        bias = torch.randn(H, L, L, device="cuda", dtype=torch.bfloat16) * 0.5
+
+    cols, seeds = [], []
+    for c in range(L // 64):
+        torch.manual_seed(13)
+        o_c, _, seed_c = ops.flash_attn_fwd(
+            q, k, _identity_block_v(BH, L, c), bias, 1, None, 1, p, True)
+        cols.append(o_c != 0)
+        seeds.append(int(seed_c))
+    keep = torch.cat(cols, dim=-1).float()  # (BH, L, L)
+    assert len(set(seeds)) == 1, seeds
+    # binomial 5-sigma band around 1 - p (the 16-bit threshold moves the
+    # rate by less than 2^-16)
+    rate = keep.mean().item()
+    sigma = math.sqrt(p * (1.0 - p) / keep.numel())
+    assert abs(rate - (1.0 - p)) < 5.0 * sigma + 2.0 ** -16, (rate, sigma)
+
+    torch.manual_seed(13)
+    o, lse, seed = ops.flash_attn_fwd(q, k, v, bias, 1, None, 1, p, True)
+    assert int(seed) == seeds[0]
+    d_out = torch.randn_like(o) * 0.3
+    dq, dk, dv = ops.flash_attn_bwd(
+        d_out, q, k, v, o, lse, bias, 1, False, None, 1, p, True, int(seed)
+    )
+
+    qr = q.float().view(B, H, L, 64).requires_grad_(True)
+    kr = k.float().view(B, H, L, 64).requires_grad_(True)
+    vr = v.float().view(B, H, L, 64).requires_grad_(True)
+    s = qr @ kr.transpose(-1, -2)
+    if with_bias:
+        s = s + bias.float().unsqueeze(0)
+    pd = torch.softmax(s, dim=-1) * keep.view(B, H, L, L) / (1.0 - p)
+    ref = pd @ vr
+    ref.backward(d_out.float().view(B, H, L, 64))
+
+    def cmp(a, b, tol, what):
+        d = (a.float().view_as(b) - b).abs().max().item()
+        scale = b.abs().max().item() + 1e-6
+        assert d / scale < tol, f"{what}: {d} vs scale {scale}"
+
+    cmp(o, ref.detach(), 0.03, "o")
+    cmp(dq, qr.grad, 0.06, "dq")
+    cmp(dk, kr.grad, 0.06, "dk")
+    cmp(dv, vr.grad, 0.06, "dv")
+
+
+@requires_gpu
+@pytest.mark.parametrize("L", [192, 576])
+def test_flash_double_run_bitwise(L):
+    """Same seed, same bits: forward and backward with dropout, bias and
+    mask, including the materialised bias gradient."""
+    from unicore_amd import ops
+
+    torch.manual_seed(6)
+    B, H, p = 2, 3, 0.3
+    q = torch.randn(B * H, L, 64, device="cuda", dtype=torch.bfloat16) * 0.2
+    k, v = torch.randn_like(q), torch.randn_like(q)
+    bias = torch.randn(H, L, L, device="cuda", dtype=torch.bfloat16) * 0.5
+    mask = torch.zeros(B, 1, L, device="cuda", dtype=torch.bfloat16)
+    mask[:, :, -9:] = -1e4
+    d_out = torch.randn_like(q) * 0.3
+
+    def run():
+        torch.manual_seed(17)
+        o, lse, seed = ops.flash_attn_fwd(q, k, v, bias, 1, mask, H, p, True)
+        grads = ops.flash_attn_bwd(
+            d_out, q, k, v, o, lse, bias, 1, True, mask, H, p, True, int(seed)
+        )
+        return (o, lse, *grads), int(seed)
+
+    first, seed1 = run()
+    second, seed2 = run()
+    assert seed1 == seed2
+    assert len(first) == 6  # o, lse, dq, dk, dv, dbias
+    for name, a, b in zip(("o", "lse", "dq", "dk", "dv", "dbias"),
+                          first, second):
+        assert torch.equal(a, b), name
+
+
+@requires_gpu
+def test_flash_bwd_rejects_bad_inputs():
+    """The backward validates what the forward validates, before any launch."""
+    from unicore_amd import ops
+
+    def inputs(L):
+        q = torch.randn(4, L, 64, device="cuda", dtype=torch.bfloat16)
+        lse = torch.zeros(4, L, device="cuda", dtype=torch.float32)
+        return dict(d_out=q.clone(), q=q, k=q.clone(), v=q.clone(),
+                    o=q.clone(), lse=lse)
+
+    def bwd(t):
+        return ops.flash_attn_bwd(t["d_out"], t["q"], t["k"], t["v"], t["o"],
+                                  t["lse"], None, 1, False, None, 1, 0.0,
+                                  False, 0)
+
+    t = inputs(64)
+    t["d_out"] = t["d_out"].float()
+    with pytest.raises(RuntimeError):
+        bwd(t)
+    with pytest.raises(RuntimeError):
+        bwd(inputs(96))
+    t = inputs(64)
+    t["lse"] = torch.zeros(4, 32, device="cuda", dtype=torch.float32)
+    with pytest.raises(RuntimeError):
+        bwd(t)
 
 
 @requires_gpu

@@ -59,7 +59,7 @@ def main():
 
     from unicore_amd.modules.multihead_attention import _FlashAttn
 
-    def fl_fb():
+    def fl_fb(q=q, k=k, v=v, bias=bias):
         qq = q.detach().requires_grad_(True)
         kk = k.detach().requires_grad_(True)
         vv = v.detach().requires_grad_(True)
@@ -69,6 +69,16 @@ def main():
 
     print(f"materialized f+b: {timeit(mat_fb, iters=10):8.2f} ms")
     print(f"flash f+b:        {timeit(fl_fb, iters=10):8.2f} ms")
+
+    # L = 448 (L % 128 != 0) is the one timed shape whose dq runs the
+    # K^T-resident 16-row kernel instead of the 32-row one
+    L2 = 448
+    q2 = torch.randn(BH, L2, D, device="cuda", dtype=torch.bfloat16) * 0.2
+    k2, v2 = torch.randn_like(q2), torch.randn_like(q2)
+    bias2 = torch.randn(H, L2, L2, device="cuda", dtype=torch.bfloat16)
+    ms = timeit(lambda: fl_fb(q2, k2, v2, bias2), iters=10)
+    print(f"flash f+b L=448:  {ms:8.2f} ms")
+    del q2, k2, v2, bias2
 
     # memory: flash never materializes the score matrix
     torch.cuda.reset_peak_memory_stats()
@@ -141,13 +151,48 @@ def long_seq():
               f"f+b flash {fl_fb_ms:8.2f} / mat {mat_fb_s}")
 
 
+def flag_sweep():
+    """Backward alone (Di + dq + dkv) per bias / mask / dropout instantiation,
+    at L = 448 (dq with K^T resident) and L = 1024 (the tiled dq and dkv):
+    the short lines above only ever run bias + dropout."""
+    from unicore_amd import ops
+
+    H, D = 8, 64
+    for L, B in ((448, 96), (1024, 16)):
+        BH = B * H
+        q = torch.randn(BH, L, D, device="cuda", dtype=torch.bfloat16) * 0.2
+        k, v = torch.randn_like(q), torch.randn_like(q)
+        d_out = torch.randn_like(q) * 0.3
+        for hb, hm, dr in ((0, 0, 0), (0, 0, 1), (0, 1, 0), (0, 1, 1),
+                           (1, 0, 0), (1, 1, 1)):
+            bias = mask = None
+            if hb:
+                bias = torch.randn(H, L, L, device="cuda", dtype=torch.bfloat16)
+            if hm:
+                mask = torch.zeros(B, 1, L, device="cuda", dtype=torch.bfloat16)
+                mask[:, :, -9:] = -1e4
+            p = 0.1 if dr else 0.0
+            o, lse, seed = ops.flash_attn_fwd(q, k, v, bias, 1, mask, H, p, True)
+            seed = int(seed)
+
+            def bwd():
+                return ops.flash_attn_bwd(d_out, q, k, v, o, lse, bias, 1, False,
+                                          mask, H, p, bool(dr), seed)
+
+            ms = timeit(bwd, iters=20, warmup=5)
+            print(f"L={L:5d} bias={hb} mask={hm} drop={dr}: bwd {ms:7.3f} ms")
+
+
 if __name__ == "__main__":
     import argparse
 
     ap = argparse.ArgumentParser()
     ap.add_argument("--long-seq", action="store_true")
+    ap.add_argument("--flag-sweep", action="store_true")
     a = ap.parse_args()
     if a.long_seq:
         long_seq()
+    elif a.flag_sweep:
+        flag_sweep()
     else:
         main()

@@ -249,9 +249,10 @@ class SelfMultiheadAttention(nn.Module):
 
         # flash path: bf16, head_dim 64, L % 64 == 0, kernel-expressible
         # bias/mask broadcasts — the L x L score matrix never hits HBM.
-        # Opt-in (UNICORE_FLASH_ATTN=1): correct and fully tested, but the
-        # v1 tile structure does not yet beat hipBLASLt bmm + the fused
-        # softmax on BERT-base shapes (see profiles/README.md).
+        # Always on under no_grad and at tgt_len >= 4096; opt-in
+        # (UNICORE_FLASH_ATTN=1) for training below that, where the tile
+        # structure does not yet beat hipBLASLt bmm + the fused softmax on
+        # BERT-base shapes (see profiles/README.md).
         o = None
         if (
             use_fused_split
