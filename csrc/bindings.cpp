@@ -101,6 +101,18 @@ std::vector<at::Tensor> flash_attn_backward(
     at::Tensor lse, std::optional<at::Tensor> bias, int64_t bias_outer_div,
     bool bias_needs_grad, std::optional<at::Tensor> mask, int64_t mask_outer_div,
     double dropout_p, bool dropped, int64_t seed_in);
+std::vector<at::Tensor> evo_attn_forward(at::Tensor q, at::Tensor k, at::Tensor v,
+                                         std::optional<at::Tensor> bias,
+                                         int64_t bias_outer_div,
+                                         std::optional<at::Tensor> mask,
+                                         int64_t mask_outer_div,
+                                         double dropout_p, bool is_training);
+std::vector<at::Tensor> evo_attn_backward(
+    at::Tensor d_out, at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o,
+    at::Tensor lse, std::optional<at::Tensor> bias, int64_t bias_outer_div,
+    bool want_dbias, std::optional<at::Tensor> mask, int64_t mask_outer_div,
+    double dropout_p, bool dropped, int64_t seed_in);
+bool evo_attn_supported(int64_t N, int64_t T, int64_t D, bool is_bf16);
 at::Tensor tri_contract(at::Tensor a, at::Tensor b);
 at::Tensor opm_forward(at::Tensor a, at::Tensor b, double scale);
 at::Tensor opm_backward_a(at::Tensor d_o, at::Tensor b, double scale);
@@ -184,6 +196,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "flash attention forward (bf16, D=64) -> (o, lse, seed)");
   m.def("flash_attn_backward", &flash_attn_backward,
         "flash attention backward -> (dq, dk, dv[, dS])");
+  m.def("evo_attn_forward", &evo_attn_forward,
+        "Evoformer attention forward (bf16, D=32, T<=512) -> (o, lse, seed)");
+  m.def("evo_attn_backward", &evo_attn_backward,
+        "Evoformer attention backward -> (dq, dk, dv[, dbias])");
+  m.def("evo_attn_supported", &evo_attn_supported,
+        "the shape / dtype checks of the Evoformer attention entries");
   m.def("dropout_add_ln_forward", &dropout_add_ln_forward,
         "fused dropout+residual+LayerNorm forward");
   m.def("dropout_add_forward", &dropout_add_forward,

@@ -38,6 +38,7 @@ from unicore_amd.modules import (
 )
 from unicore_amd.modules.dropout_add_ln import dropout_add_ln_pre
 from unicore_amd.modules.embedding import Embedding
+from unicore_amd.modules.evo_attention import evo_attention
 from unicore_amd.modules.padding_mask import build_evoformer_masks
 from unicore_amd.modules.triangle_attention import TriangleAttention
 
@@ -84,12 +85,17 @@ class MSARowAttentionWithPairBias(nn.Module):
         q = arrange(q) * self.scaling
         k = arrange(k)
         v = arrange(v)
-        scores = qk_scores(q, k).view(B, H, S, L, L)
         bias = self.pair_bias(self.pair_norm(pair))  # (B, L, L, H)
         bias = bias.permute(0, 3, 1, 2).unsqueeze(2)  # (B, H, 1, L, L)
-        attn = softmax_dropout(scores, self.dropout, self.training,
-                               mask=key_mask, bias=bias)
-        o = torch.bmm(attn.view(B * H * S, L, L), v)
+        # head dim 32: scores stay on chip (UNICORE_EVO_ATTN)
+        o = evo_attention(q.view(B, H, S, L, Dh), k.view(B, H, S, L, Dh),
+                          v.view(B, H, S, L, Dh), bias, key_mask, self.dropout,
+                          self.training)
+        if o is None:
+            scores = qk_scores(q, k).view(B, H, S, L, L)
+            attn = softmax_dropout(scores, self.dropout, self.training,
+                                   mask=key_mask, bias=bias)
+            o = torch.bmm(attn.view(B * H * S, L, L), v)
         o = msa_merge(o, B, S, L, H, col=False)
         if _fold_ok(self.gate.bias):
             og = gated_mul(o, F.linear(x, self.gate.weight),
@@ -127,15 +133,20 @@ class MSAColumnAttention(nn.Module):
         q = arrange(q) * self.scaling
         k = arrange(k)
         v = arrange(v)
-        scores = qk_scores(q, k).view(B * L * H, S, S)
-        if key_mask is None:
-            attn = softmax_dropout(scores, self.dropout, self.training)
-        else:
-            # msa_arrange(col=True) orders the batches (B, L, H)
-            attn = softmax_dropout(scores.view(B, L, H, S, S), self.dropout,
-                                   self.training, mask=key_mask)
-            attn = attn.view(B * L * H, S, S)
-        o = torch.bmm(attn, v)
+        # msa_arrange(col=True) orders the batches (B, L, H); head dim 32:
+        # scores stay on chip (UNICORE_EVO_ATTN)
+        o = evo_attention(q.view(B, L, H, S, Dh), k.view(B, L, H, S, Dh),
+                          v.view(B, L, H, S, Dh), None, key_mask, self.dropout,
+                          self.training)
+        if o is None:
+            scores = qk_scores(q, k).view(B * L * H, S, S)
+            if key_mask is None:
+                attn = softmax_dropout(scores, self.dropout, self.training)
+            else:
+                attn = softmax_dropout(scores.view(B, L, H, S, S), self.dropout,
+                                       self.training, mask=key_mask)
+                attn = attn.view(B * L * H, S, S)
+            o = torch.bmm(attn, v)
         o = msa_merge(o, B, S, L, H, col=True)
         if _fold_ok(self.gate.bias):
             og = gated_mul(o, F.linear(x, self.gate.weight),

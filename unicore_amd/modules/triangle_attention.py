@@ -34,6 +34,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .evo_attention import evo_attention
 from .gated_mul import gated_mul
 from .layer_norm import LayerNorm
 from .multihead_attention import qk_scores
@@ -256,13 +257,18 @@ class TriangleAttention(nn.Module):
         q, k, v = (t.view(B * H * R, T, D)
                    for t in pair_arrange_qkv(self.qkv(p), H, tr))
         q = q * self.scaling
-        scores = qk_scores(q, k).view(B, H, R, T, T)
         bias = pair_bias_arrange(self.bias_proj(p), tr).unsqueeze(2)
         if key_mask is None and pair_mask is not None:
-            key_mask = triangle_key_mask(pair_mask, scores.dtype, self.starting)
-        attn = softmax_dropout(scores, self.dropout, self.training,
-                               mask=key_mask, bias=bias)
-        o = torch.bmm(attn.view(B * H * R, T, T), v)
+            key_mask = triangle_key_mask(pair_mask, q.dtype, self.starting)
+        # head dim 32: scores stay on chip (UNICORE_EVO_ATTN)
+        o = evo_attention(q.view(B, H, R, T, D), k.view(B, H, R, T, D),
+                          v.view(B, H, R, T, D), bias, key_mask, self.dropout,
+                          self.training)
+        if o is None:
+            scores = qk_scores(q, k).view(B, H, R, T, T)
+            attn = softmax_dropout(scores, self.dropout, self.training,
+                                   mask=key_mask, bias=bias)
+            o = torch.bmm(attn.view(B * H * R, T, T), v)
         o = pair_merge(o, B, I, J, H, tr)
         if _fold_ok(self.gate.bias):
             og = gated_mul(o, F.linear(p, self.gate.weight),

@@ -178,6 +178,36 @@ def flash_attn_bwd(d_out, q, k, v, o, lse, bias, bias_outer_div, bias_needs_grad
     )
 
 
+def evo_attn_fwd(q, k, v, bias, bias_od, mask, mask_od, p, training):
+    """q, k, v: (N, T, 32) contiguous bf16, q pre-scaled; bias (nb, T, T) /
+    mask (nb, 1, T) bf16 with the softmax_dropout broadcast contract.
+    Returns (o, lse, seed)."""
+    require_kernels()
+    return _kernels.evo_attn_forward(
+        q, k, v, bias, int(bias_od), mask, int(mask_od), float(p), bool(training)
+    )
+
+
+def evo_attn_bwd(d_o, q, k, v, o, lse, bias, bias_od, want_dbias, mask, mask_od,
+                 p, dropped, seed):
+    """Returns (dq, dk, dv) and, with want_dbias, the fp32 (nb, T, T) dbias."""
+    require_kernels()
+    return _kernels.evo_attn_backward(
+        d_o, q, k, v, o, lse, bias, int(bias_od), bool(want_dbias), mask,
+        int(mask_od), float(p), bool(dropped), int(seed)
+    )
+
+
+def evo_attn_supported(N, T, D, dtype):
+    """The shape / dtype half of the host checks of evo_attn_fwd / _bwd."""
+    import torch
+
+    require_kernels()
+    return _kernels.evo_attn_supported(
+        int(N), int(T), int(D), dtype == torch.bfloat16
+    )
+
+
 def dropout_add_ln_fwd(x, res, bias, gamma, beta, p, is_training, eps):
     require_kernels()
     return _kernels.dropout_add_ln_forward(
