@@ -113,6 +113,14 @@ std::vector<at::Tensor> evo_attn_backward(
     bool want_dbias, std::optional<at::Tensor> mask, int64_t mask_outer_div,
     double dropout_p, bool dropped, int64_t seed_in);
 bool evo_attn_supported(int64_t N, int64_t T, int64_t D, bool is_bf16);
+std::vector<at::Tensor> pair_attn_forward(at::Tensor q, at::Tensor k,
+                                          at::Tensor v, at::Tensor bias,
+                                          double dropout_p, bool is_training);
+std::vector<at::Tensor> pair_attn_backward(
+    at::Tensor d_out, std::optional<at::Tensor> d_logits, at::Tensor q,
+    at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor lse, at::Tensor logits,
+    double dropout_p, bool dropped, int64_t seed_in);
+bool pair_attn_supported(int64_t L, int64_t D, bool is_bf16);
 at::Tensor tri_contract(at::Tensor a, at::Tensor b);
 at::Tensor opm_forward(at::Tensor a, at::Tensor b, double scale);
 at::Tensor opm_backward_a(at::Tensor d_o, at::Tensor b, double scale);
@@ -202,6 +210,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Evoformer attention backward -> (dq, dk, dv[, dbias])");
   m.def("evo_attn_supported", &evo_attn_supported,
         "the shape / dtype checks of the Evoformer attention entries");
+  m.def("pair_attn_forward", &pair_attn_forward,
+        "pair-track attention forward (bf16, D=64, L<=512) -> (o, logits, "
+        "lse, seed)");
+  m.def("pair_attn_backward", &pair_attn_backward,
+        "pair-track attention backward -> (dq, dk, dv, dbias)");
+  m.def("pair_attn_supported", &pair_attn_supported,
+        "the shape / dtype checks of the pair-track attention entries");
   m.def("dropout_add_ln_forward", &dropout_add_ln_forward,
         "fused dropout+residual+LayerNorm forward");
   m.def("dropout_add_forward", &dropout_add_forward,

@@ -41,6 +41,7 @@ HIP_SOURCES = [
     "csrc/outer_product.hip",
     "csrc/tri_attn.hip",
     "csrc/pair_coord.hip",
+    "csrc/pair_attn.hip",
 ]
 
 setup(

@@ -125,8 +125,8 @@ class PairBiasEncoderLayer(nn.Module):
         x = self.attn_norm(x)
         attn_weights = None
         if return_pair:
-            x, attn_weights, _ = self.attn(x, attn_bias=bias, return_attn=True,
-                                           skip_out_bias=fold)
+            x, attn_weights = self.attn(x, attn_bias=bias, return_logits=True,
+                                        skip_out_bias=fold)
         else:
             x = self.attn(x, attn_bias=bias, skip_out_bias=fold)
         x = dropout_add(

@@ -15,6 +15,7 @@ from torch import Tensor, nn
 
 import os
 
+from .pair_attention import pair_attention
 from .softmax_dropout import _broadcast_descr, softmax_dropout
 
 
@@ -212,10 +213,16 @@ class SelfMultiheadAttention(nn.Module):
 
     def forward(self, query, key_padding_mask: Optional[Tensor] = None,
                 attn_bias: Optional[Tensor] = None, return_attn: bool = False,
-                skip_out_bias: bool = False) -> Tensor:
+                skip_out_bias: bool = False,
+                return_logits: bool = False) -> Tensor:
         """``skip_out_bias``: run out_proj without its bias — the caller
         folds it into the following fused dropout+residual op (which then
-        also produces the bias gradient)."""
+        also produces the bias gradient).
+
+        ``return_logits``: return ``(attn_out, logits)``, the pre-softmax
+        attention logits (B, H, L, L) without the probabilities; served by
+        the fused pair-track attention (pair_attention.py) where it applies,
+        by the ``return_attn`` chain otherwise."""
         bsz, tgt_len, embed_dim = query.shape
         assert embed_dim == self.embed_dim, "input width mismatch"
 
@@ -254,8 +261,18 @@ class SelfMultiheadAttention(nn.Module):
         # structure does not yet beat hipBLASLt bmm + the fused softmax on
         # BERT-base shapes (see profiles/README.md).
         o = None
+        logits = None
+        if return_logits and not return_attn:
+            fused = pair_attention(
+                q, k, v, attn_bias, bsz, self.num_heads, self.dropout,
+                self.training, key_padding_mask=mask,
+            )
+            if fused is not None:
+                o, logits = fused
+        want_weights = return_attn or return_logits
         if (
-            use_fused_split
+            o is None
+            and use_fused_split
             # opt-in for training at short L; always on under no_grad
             # (forward-only flash is ~1.4-3.8x the materialized chain) and
             # for long sequences, where the measured fwd+bwd crossover sits
@@ -263,7 +280,7 @@ class SelfMultiheadAttention(nn.Module):
             # (tools/flash_microbench.py --long-seq)
             and (_flash_enabled() or not torch.is_grad_enabled()
                  or tgt_len >= 4096)
-            and not return_attn
+            and not want_weights
             and q.dtype == torch.bfloat16
             and self.head_dim == 64
             and tgt_len == src_len
@@ -291,7 +308,7 @@ class SelfMultiheadAttention(nn.Module):
             scores = qk_scores(q, k)
             assert scores.shape == (bsz * self.num_heads, tgt_len, src_len)
             scores = scores.view(bsz, self.num_heads, tgt_len, src_len)
-            if return_attn:
+            if want_weights:
                 attn_weights = scores + (0 if mask is None else mask)
                 if attn_bias is not None:
                     attn_weights = attn_weights + attn_bias
@@ -320,6 +337,8 @@ class SelfMultiheadAttention(nn.Module):
             attn_out = self.out_proj(attn_out)
         if return_attn:
             return attn_out, attn_weights, attn
+        if return_logits:
+            return attn_out, attn_weights if logits is None else logits
         return attn_out
 
 

@@ -208,6 +208,32 @@ def evo_attn_supported(N, T, D, dtype):
     )
 
 
+def pair_attn_fwd(q, k, v, bias, p, training):
+    """q, k, v: (B*H, L, 64) contiguous bf16, q pre-scaled; bias (B, H, L, L)
+    bf16, padded keys at finfo.min.  Returns (o, logits, lse, seed): logits
+    = bf16(fp32(q k^T) + bias), the softmax taken from the rounded logits."""
+    require_kernels()
+    return _kernels.pair_attn_forward(q, k, v, bias, float(p), bool(training))
+
+
+def pair_attn_bwd(d_o, d_logits, q, k, v, o, lse, logits, p, dropped, seed):
+    """d_logits: the gradient arriving at the returned logits, or None.
+    Returns (dq, dk, dv, dbias), dbias bf16 in the shape of the bias."""
+    require_kernels()
+    return _kernels.pair_attn_backward(
+        d_o, d_logits, q, k, v, o, lse, logits, float(p), bool(dropped),
+        int(seed)
+    )
+
+
+def pair_attn_supported(L, D, dtype):
+    """The shape / dtype half of the host checks of pair_attn_fwd / _bwd."""
+    import torch
+
+    require_kernels()
+    return _kernels.pair_attn_supported(int(L), int(D), dtype == torch.bfloat16)
+
+
 def dropout_add_ln_fwd(x, res, bias, gamma, beta, p, is_training, eps):
     require_kernels()
     return _kernels.dropout_add_ln_forward(
