@@ -11,9 +11,19 @@
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
+#include <cfloat>
 #include <vector>
 
 namespace {
+
+// An online-logsumexp state (m, s) starts at (LSE_EMPTY, 0).  The running
+// maximum is a finite sentinel, not -inf, so that `v - m` is never
+// `-inf - -inf`: a -inf logit adds exp(-inf) = 0 whether or not the state has
+// seen a finite one.  A state that saw nothing (V < blockDim) or only -inf has
+// s == 0, which is what lse_combine tests: a state that saw only NaN still
+// has the empty maximum, but its s is NaN and has to be carried on.  +inf
+// makes m = +inf and the row's lse non-finite.
+constexpr float LSE_EMPTY = -FLT_MAX;
 
 // combine two (m, s) online-logsumexp states
 __device__ __forceinline__ void lse_combine(float& m, float& s, float m2,
@@ -21,12 +31,13 @@ __device__ __forceinline__ void lse_combine(float& m, float& s, float m2,
   if (m2 > m) {
     s = s * __expf(m - m2) + s2;
     m = m2;
-  } else if (m2 != -INFINITY) {
+  } else if (s2 != 0.f) {
     s = s + s2 * __expf(m2 - m);
   }
-  // m2 == -INFINITY and m2 <= m: empty state, nothing to add (guards the
-  // exp(-inf - -inf) = NaN case when V < blockDim and some lanes saw no
-  // elements)
+}
+
+inline bool aligned16(const at::Tensor& t) {
+  return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
 }
 
 template <typename T, bool VEC8>
@@ -41,7 +52,7 @@ __global__ void ce_fwd_kernel(float* __restrict__ loss, float* __restrict__ lse,
   const int lane = tid & 63;
   for (int64_t row = blockIdx.x; row < n_rows; row += gridDim.x) {
     const T* x = logits + row * V;
-    float m = -INFINITY, s = 0.f;
+    float m = LSE_EMPTY, s = 0.f;
     int64_t e = tid * 8;
     if constexpr (VEC8) {
       for (; e + 7 < V; e += 256 * 8) {
@@ -134,6 +145,18 @@ __global__ void ce_bwd_kernel(T* __restrict__ dx, const T* __restrict__ logits,
   }
 }
 
+void ce_check_target(const at::Tensor& target, const at::Tensor& logits,
+                     const char* who) {
+  TORCH_CHECK(target.scalar_type() == at::kLong, who,
+              ": target must be int64, got ", target.scalar_type());
+  TORCH_CHECK(target.is_contiguous() && target.numel() == logits.size(0), who,
+              ": target must be contiguous with ", logits.size(0),
+              " elements (one per row), got ", target.numel(),
+              target.is_contiguous() ? "" : ", not contiguous");
+  TORCH_CHECK(target.device() == logits.device(), who, ": target is on ",
+              target.device(), ", logits on ", logits.device());
+}
+
 }  // namespace
 
 // returns (per-row loss fp32 (N,), per-row lse fp32 (N,))
@@ -141,17 +164,18 @@ std::vector<at::Tensor> cross_entropy_forward(at::Tensor logits, at::Tensor targ
                                               int64_t ignore_index) {
   TORCH_CHECK(logits.is_cuda() && logits.is_contiguous() && logits.dim() == 2,
               "cross_entropy: logits must be contiguous (N, V)");
-  TORCH_CHECK(target.scalar_type() == at::kLong &&
-                  target.numel() == logits.size(0),
-              "cross_entropy: bad target");
+  ce_check_target(target, logits, "cross_entropy");
   const int64_t N = logits.size(0);
   const int64_t V = logits.size(1);
+  // load8 needs 16 B: a contiguous view into a larger buffer may start
+  // anywhere, and takes the scalar instantiation
+  const bool vec8 = V % 8 == 0 && aligned16(logits);
   auto fopt = logits.options().dtype(at::kFloat);
   auto loss = at::empty({N}, fopt);
   auto lse = at::empty({N}, fopt);
   auto stream = at::cuda::getCurrentCUDAStream();
   DISPATCH_FTYPES(logits.scalar_type(), "cross_entropy_forward", {
-    if (V % 8 == 0)
+    if (vec8)
       ce_fwd_kernel<scalar_t, true><<<unicore_grid(N), 256, 0, stream>>>(
           loss.data_ptr<float>(), lse.data_ptr<float>(),
           reinterpret_cast<const scalar_t*>(logits.data_ptr()),
@@ -171,14 +195,30 @@ at::Tensor cross_entropy_backward(at::Tensor logits, at::Tensor target,
                                   int64_t ignore_index) {
   TORCH_CHECK(logits.is_cuda() && logits.is_contiguous() && logits.dim() == 2,
               "cross_entropy_backward: logits must be contiguous (N, V)");
-  TORCH_CHECK(grad_scale.scalar_type() == at::kFloat && grad_scale.numel() == 1,
-              "cross_entropy_backward: grad_scale must be fp32 scalar");
+  TORCH_CHECK(grad_scale.scalar_type() == at::kFloat &&
+                  grad_scale.numel() == 1 &&
+                  grad_scale.device() == logits.device(),
+              "cross_entropy_backward: grad_scale must be one fp32 number on ",
+              logits.device(), ", got ", grad_scale.scalar_type(), " x ",
+              grad_scale.numel(), " on ", grad_scale.device());
+  ce_check_target(target, logits, "cross_entropy_backward");
   const int64_t N = logits.size(0);
   const int64_t V = logits.size(1);
+  TORCH_CHECK(lse.scalar_type() == at::kFloat,
+              "cross_entropy_backward: lse must be fp32, got ",
+              lse.scalar_type());
+  TORCH_CHECK(lse.is_contiguous() && lse.numel() == N,
+              "cross_entropy_backward: lse must be contiguous with ", N,
+              " elements (one per row), got ", lse.numel(),
+              lse.is_contiguous() ? "" : ", not contiguous");
+  TORCH_CHECK(lse.device() == logits.device(),
+              "cross_entropy_backward: lse is on ", lse.device(),
+              ", logits on ", logits.device());
   auto dx = at::empty_like(logits);
+  const bool vec8 = V % 8 == 0 && aligned16(logits) && aligned16(dx);
   auto stream = at::cuda::getCurrentCUDAStream();
   DISPATCH_FTYPES(logits.scalar_type(), "cross_entropy_backward", {
-    if (V % 8 == 0)
+    if (vec8)
       ce_bwd_kernel<scalar_t, true><<<unicore_grid(N), 256, 0, stream>>>(
           reinterpret_cast<scalar_t*>(dx.data_ptr()),
           reinterpret_cast<const scalar_t*>(logits.data_ptr()),

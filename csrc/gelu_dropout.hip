@@ -102,16 +102,41 @@ __global__ void gelu_dropout_bwd_kernel(T* __restrict__ dx, const T* __restrict_
   }
 }
 
+// There is no scalar kernel: every tensor is moved with load8 / store8, so
+// each must start on a 16 B boundary (a contiguous view into a larger buffer
+// need not; the module shim hands such a view over as an aligned copy).
+void check_aligned16(const at::Tensor& t, const char* who, const char* name) {
+  const auto addr = reinterpret_cast<uintptr_t>(t.data_ptr());
+  TORCH_CHECK(addr % 16 == 0, who, ": ", name,
+              " must be 16-byte aligned, its address is ", addr % 16,
+              " bytes past a 16-byte boundary");
+}
+
+void check_bias(const at::Tensor& bc, const at::Tensor& x, const char* who) {
+  TORCH_CHECK(bc.numel() > 0 && bc.numel() % 8 == 0 && x.dim() >= 1 &&
+                  x.size(-1) == bc.numel(),
+              who, ": bias must have the last dimension of x (",
+              x.dim() >= 1 ? x.size(-1) : 0,
+              "), a positive multiple of 8, elements; got ", bc.numel());
+  TORCH_CHECK(bc.scalar_type() == x.scalar_type() && bc.device() == x.device(),
+              who, ": bias is ", bc.scalar_type(), " on ", bc.device(),
+              ", x is ", x.scalar_type(), " on ", x.device());
+  check_aligned16(bc, who, "bias");
+}
+
 }  // namespace
 
 std::vector<at::Tensor> gelu_dropout_forward(at::Tensor x,
                                              std::optional<at::Tensor> bias,
                                              double p, bool is_training) {
   TORCH_CHECK(x.is_cuda() && x.is_contiguous(), "gelu_dropout: contiguous CUDA");
-  TORCH_CHECK(x.numel() % 8 == 0, "gelu_dropout: numel % 8 == 0");
+  TORCH_CHECK(x.numel() % 8 == 0, "gelu_dropout: numel % 8 == 0, got ",
+              x.numel());
+  check_aligned16(x, "gelu_dropout", "x");
   const int64_t n8 = x.numel() / 8;
   const bool drop = is_training && p > 0.0;
   auto out = at::empty_like(x);
+  check_aligned16(out, "gelu_dropout", "out");
   auto dmask = at::empty({drop ? n8 : 0}, x.options().dtype(at::kByte));
   float pinv = 1.f;
   uint32_t pthresh = 0;
@@ -127,10 +152,8 @@ std::vector<at::Tensor> gelu_dropout_forward(at::Tensor x,
   int C = 0;
   if (has_bias) {
     bc = bias->contiguous();
+    check_bias(bc, x, "gelu_dropout");
     C = (int)bc.numel();
-    TORCH_CHECK(C > 0 && C % 8 == 0 && x.size(-1) == C &&
-                    bc.scalar_type() == x.scalar_type(),
-                "gelu_dropout: bad bias");
   }
   auto stream = at::cuda::getCurrentCUDAStream();
   const int grid = unicore_grid((n8 + 255) / 256);
@@ -160,21 +183,43 @@ std::vector<at::Tensor> gelu_dropout_forward(at::Tensor x,
 std::vector<at::Tensor> gelu_dropout_backward(at::Tensor grad, at::Tensor x,
                                               std::optional<at::Tensor> bias,
                                               at::Tensor dmask, double p) {
-  TORCH_CHECK(grad.is_cuda() && grad.is_contiguous() && x.is_contiguous(),
-              "gelu_dropout_backward: contiguous CUDA");
+  const char* who = "gelu_dropout_backward";
+  TORCH_CHECK(grad.is_cuda() && x.is_cuda() && grad.is_contiguous() &&
+                  x.is_contiguous(),
+              who, ": contiguous CUDA");
+  TORCH_CHECK(x.numel() % 8 == 0, who, ": numel % 8 == 0, got ", x.numel());
+  TORCH_CHECK(grad.sizes() == x.sizes() &&
+                  grad.scalar_type() == x.scalar_type() &&
+                  grad.device() == x.device(),
+              who, ": grad must match x; grad is ", grad.scalar_type(), " ",
+              grad.sizes(), " on ", grad.device(), ", x is ", x.scalar_type(),
+              " ", x.sizes(), " on ", x.device());
   const int64_t n8 = x.numel() / 8;
   const bool drop = dmask.defined() && dmask.numel() > 0;
+  if (drop) {
+    TORCH_CHECK(dmask.numel() == n8, who, ": dmask must be empty or hold ", n8,
+                " bytes (one per 8 elements of x), got ", dmask.numel());
+    TORCH_CHECK(dmask.scalar_type() == at::kByte && dmask.is_contiguous() &&
+                    dmask.device() == x.device(),
+                who, ": dmask must be contiguous uint8 on ", x.device(),
+                ", got ", dmask.scalar_type(), " on ", dmask.device());
+  }
+  check_aligned16(x, who, "x");
+  check_aligned16(grad, who, "grad");
   const bool bgrad = bias.has_value();
   at::Tensor bc;
   int C = 0;
   if (bgrad) {
     bc = bias->contiguous();
+    check_bias(bc, x, who);
     C = (int)bc.numel();
-    TORCH_CHECK(colsum_supported(C), "gelu_dropout_backward: bad bias dim");
+    TORCH_CHECK(colsum_supported(C), who, ": no column sum for a bias of ", C,
+                " elements");
   }
   const float pinv =
       drop ? (float)(1.0 / (1.0 - std::min(p, 0.999999))) : 1.f;
   auto dx = at::empty_like(x);
+  check_aligned16(dx, who, "dx");
   auto dbias = at::empty({bgrad ? (int64_t)C : 0},
                          grad.options().dtype(at::kFloat));
   auto stream = at::cuda::getCurrentCUDAStream();

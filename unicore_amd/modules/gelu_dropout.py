@@ -12,12 +12,19 @@ import torch
 import torch.nn.functional as F
 
 
+def _aligned(t):
+    """`t` contiguous and on a 16-byte boundary, as the kernels' vector loads
+    need it: a contiguous view into a larger buffer may start anywhere."""
+    t = t.contiguous()
+    return t.clone() if t.data_ptr() % 16 else t
+
+
 class _GeluDropout(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, bias, p, is_training):
         from unicore_amd import ops
 
-        x = x.contiguous()
+        x, bias = _aligned(x), _aligned(bias)
         out, dmask = ops.gelu_dropout_fwd(x, p, is_training, bias)
         ctx.p = p
         ctx.save_for_backward(x, dmask, bias)
@@ -28,7 +35,7 @@ class _GeluDropout(torch.autograd.Function):
         from unicore_amd import ops
 
         x, dmask, bias = ctx.saved_tensors
-        dx, db = ops.gelu_dropout_bwd(grad.contiguous(), x, dmask, ctx.p,
+        dx, db = ops.gelu_dropout_bwd(_aligned(grad), x, dmask, ctx.p,
                                       bias=bias)
         dbias = db.to(bias.dtype) if bias is not None else None
         return dx, dbias, None, None
@@ -39,7 +46,7 @@ class _GeluDropoutNoBias(torch.autograd.Function):
     def forward(ctx, x, p, is_training):
         from unicore_amd import ops
 
-        x = x.contiguous()
+        x = _aligned(x)
         out, dmask = ops.gelu_dropout_fwd(x, p, is_training)
         ctx.p = p
         ctx.save_for_backward(x, dmask)
@@ -50,7 +57,7 @@ class _GeluDropoutNoBias(torch.autograd.Function):
         from unicore_amd import ops
 
         x, dmask = ctx.saved_tensors
-        dx, _ = ops.gelu_dropout_bwd(grad.contiguous(), x, dmask, ctx.p)
+        dx, _ = ops.gelu_dropout_bwd(_aligned(grad), x, dmask, ctx.p)
         return dx, None, None
 
 
