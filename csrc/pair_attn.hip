@@ -42,6 +42,7 @@
 //   C (16x16): lane l -> col l&15,  rows (l>>4)*4+[0..4)
 #include "common.h"
 #include "dispatch.h"
+#include "pair_attn_d8.h"
 
 #include <optional>
 #include <type_traits>
@@ -510,8 +511,11 @@ PAIR_KERNEL __launch_bounds__(256) void pair_bwd_dkv_kernel(
 
 constexpr int64_t GRID_MAX = 2147483647LL;
 
+// head dim 8 has the same contract and its own kernels (pair_attn_d8.hip)
+constexpr int HD8 = 8;
+
 const char* shape_problem(int64_t L, int64_t D) {
-  if (D != HD) return "head dim must be 64";
+  if (D != HD && D != HD8) return "head dim must be 64 or 8";
   if (L < 64 || L > LMAX || L % 64 != 0)
     return "L must be a multiple of 64 in [64, 512]";
   return nullptr;
@@ -536,7 +540,7 @@ void check_tensor(const char* fn, const char* name, const at::Tensor& t,
               t.data_ptr());
 }
 
-// q first: every operand is (BH, L, 64) like it
+// q first: every operand is (BH, L, D) like it
 void check_operands(
     const char* fn,
     std::initializer_list<std::pair<const char*, const at::Tensor*>> operands) {
@@ -616,8 +620,8 @@ bool pair_attn_supported(int64_t L, int64_t D, bool is_bf16) {
   return is_bf16 && shape_problem(L, D) == nullptr;
 }
 
-// q, k, v: (B*H, L, 64) contiguous bf16, q pre-scaled; bias (B, H, L, L)
-// -> (o, logits, lse, seed)
+// q, k, v: (B*H, L, D) contiguous bf16, D 64 or 8, q pre-scaled; bias
+// (B, H, L, L) -> (o, logits, lse, seed)
 std::vector<at::Tensor> pair_attn_forward(at::Tensor q, at::Tensor k,
                                           at::Tensor v, at::Tensor bias,
                                           double dropout_p, bool is_training) {
@@ -637,6 +641,13 @@ std::vector<at::Tensor> pair_attn_forward(at::Tensor q, at::Tensor k,
   auto o = at::empty_like(q);
   auto logits = at::empty_like(bias);
   auto lse = at::empty({BH, (int64_t)L}, q.options().dtype(at::kFloat));
+  const at::Tensor seed_t =
+      at::scalar_tensor((int64_t)seed, at::TensorOptions().dtype(at::kLong));
+  if (q.size(2) == HD8) {
+    pair8_forward_launch(o, logits, lse, q, k, v, bias,
+                         Pair8Drop{drop, dr.pinv, dr.pthresh, dr.seed});
+    return {o, logits, lse, seed_t};
+  }
   auto stream = at::cuda::getCurrentCUDAStream();
   const dim3 grid((unsigned)(BH * (L / BM)));
   dispatch_pitch(
@@ -650,8 +661,7 @@ std::vector<at::Tensor> pair_attn_forward(at::Tensor q, at::Tensor k,
       drop);
   C10_CUDA_KERNEL_LAUNCH_CHECK();
   // the seed is host state: a CPU scalar costs the wrapper no sync
-  return {o, logits, lse,
-          at::scalar_tensor((int64_t)seed, at::TensorOptions().dtype(at::kLong))};
+  return {o, logits, lse, seed_t};
 }
 
 // -> (dq, dk, dv, dbias); d_logits is the gradient arriving at the returned
@@ -680,16 +690,23 @@ std::vector<at::Tensor> pair_attn_backward(
   const bool drop = dropped && dropout_p > 0.0;
   const Drop dr = make_drop(fn, drop, dropout_p, (uint64_t)seed_in);
 
+  auto dq = at::empty_like(q);
+  auto dk = at::empty_like(k);
+  auto dv = at::empty_like(v);
+  auto dbias = at::empty_like(logits);
+  if (q.size(2) == HD8) {
+    pair8_backward_launch(dq, dk, dv, dbias, d_out,
+                          has_dl ? &*d_logits : nullptr, q, k, v, o, lse,
+                          logits, Pair8Drop{drop, dr.pinv, dr.pthresh, dr.seed});
+    return {dq, dk, dv, dbias};
+  }
+
   auto stream = at::cuda::getCurrentCUDAStream();
   auto di = at::empty({BH, (int64_t)L}, q.options().dtype(at::kFloat));
   const int64_t n_rows = BH * L;
   pair_dot_do_o_kernel<<<unicore_grid((n_rows + 31) / 32), 256, 0, stream>>>(
       di.data_ptr<float>(), bits(d_out), bits(o), n_rows);
 
-  auto dq = at::empty_like(q);
-  auto dk = at::empty_like(k);
-  auto dv = at::empty_like(v);
-  auto dbias = at::empty_like(logits);
   const float* lse_p = lse.data_ptr<float>();
   const uint16_t* dl_p = has_dl ? bits(*d_logits) : nullptr;
   const dim3 grid((unsigned)(BH * (L / BM)));

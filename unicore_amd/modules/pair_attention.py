@@ -1,4 +1,5 @@
-"""Fused attention of the pair track (csrc/pair_attn.hip): bf16, head dim 64,
+"""Fused attention of the pair track (csrc/pair_attn.hip, head dim 64;
+csrc/pair_attn_d8.hip, head dim 8 = Uni-Mol's 64 heads at embed 512): bf16,
 L % 64 == 0, 64 <= L <= 512, a full per-head (B, H, L, L) bias.
 
     logits = bf16(fp32(q k^T) + bias)       returned: the next pair state
@@ -8,8 +9,10 @@ L % 64 == 0, 64 <= L <= 512, a full per-head (B, H, L, L) bias.
 not serve the call; ``SelfMultiheadAttention`` then runs the bmm -> add ->
 ``softmax_dropout`` -> bmm chain as before.
 
-Gate: ``UNICORE_PAIR_ATTN``, read per call (docs/KERNELS.md, "Pair-track
-attention", has the measurement behind its default).
+Gates: ``UNICORE_PAIR_ATTN`` for every head dim and ``UNICORE_PAIR_ATTN_D8``
+for head dim 8 alone, read per call (docs/KERNELS.md, "Pair-track attention"
+and "Pair-track attention, head dim 8", have the measurements behind their
+defaults).
 """
 
 import os
@@ -22,6 +25,14 @@ import torch
 # 21 us between repeated gate-0 rounds; the stress command with --coord-head
 # equivariant 81.7 -> 85.3 ups.
 _PAIR_ATTN_DEFAULT = "1"
+
+# default of the UNICORE_PAIR_ATTN_D8 gate (head dim 8, csrc/pair_attn_d8.hip):
+# on.  Same-box figures (profiles/mol_pair_attn_d8.txt): forward+backward of
+# the module at B 32, H 64 is 789 -> 335 us at L 128 and 1862 -> 645 us at
+# L 256, against a spread of 1.7 / 1.3 us between repeated gate-0 rounds; the
+# stress command with --coord-head equivariant --encoder-attention-heads 64
+# 20.9 -> 32.1 ups.
+_PAIR_ATTN_D8_DEFAULT = "1"
 
 
 class _PairAttn(torch.autograd.Function):
@@ -65,6 +76,13 @@ def pair_enabled() -> bool:
     return os.environ.get("UNICORE_PAIR_ATTN", _PAIR_ATTN_DEFAULT) == "1"
 
 
+def pair_d8_enabled() -> bool:
+    """Head dim 8 needs both gates: UNICORE_PAIR_ATTN=0 turns off every head
+    dim, UNICORE_PAIR_ATTN_D8=0 this one."""
+    return pair_enabled() and os.environ.get(
+        "UNICORE_PAIR_ATTN_D8", _PAIR_ATTN_D8_DEFAULT) == "1"
+
+
 def pair_attention(q, k, v, attn_bias, bsz, heads, p, training,
                    key_padding_mask=None):
     """q, k, v: (bsz*heads, L, D), q pre-scaled; attn_bias (bsz, heads, L, L)
@@ -79,6 +97,8 @@ def pair_attention(q, k, v, attn_bias, bsz, heads, p, training,
     if q.dim() != 3 or k.shape != q.shape or v.shape != q.shape:
         return None
     L, D = q.shape[1], q.shape[2]
+    if D == 8 and not pair_d8_enabled():
+        return None
     if q.shape[0] != bsz * heads or tuple(attn_bias.shape) != (bsz, heads, L, L):
         return None
     if attn_bias.dtype != q.dtype or attn_bias.device != q.device:

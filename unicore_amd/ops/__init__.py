@@ -209,9 +209,10 @@ def evo_attn_supported(N, T, D, dtype):
 
 
 def pair_attn_fwd(q, k, v, bias, p, training):
-    """q, k, v: (B*H, L, 64) contiguous bf16, q pre-scaled; bias (B, H, L, L)
-    bf16, padded keys at finfo.min.  Returns (o, logits, lse, seed): logits
-    = bf16(fp32(q k^T) + bias), the softmax taken from the rounded logits."""
+    """q, k, v: (B*H, L, D) contiguous bf16, D 64 (csrc/pair_attn.hip) or 8
+    (csrc/pair_attn_d8.hip), q pre-scaled; bias (B, H, L, L) bf16, padded keys
+    at finfo.min.  Returns (o, logits, lse, seed): logits = bf16(fp32(q k^T)
+    + bias), the softmax taken from the rounded logits."""
     require_kernels()
     return _kernels.pair_attn_forward(q, k, v, bias, float(p), bool(training))
 
@@ -227,7 +228,8 @@ def pair_attn_bwd(d_o, d_logits, q, k, v, o, lse, logits, p, dropped, seed):
 
 
 def pair_attn_supported(L, D, dtype):
-    """The shape / dtype half of the host checks of pair_attn_fwd / _bwd."""
+    """The shape / dtype half of the host checks of pair_attn_fwd / _bwd:
+    bf16, D 64 or 8, L a multiple of 64 in [64, 512]."""
     import torch
 
     require_kernels()
