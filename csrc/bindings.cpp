@@ -159,7 +159,8 @@ std::vector<at::Tensor> pair_coord_backward(
     at::Tensor grad, at::Tensor pair, at::Tensor pair0, at::Tensor coords,
     at::Tensor inv_n, std::optional<at::Tensor> pad, at::Tensor W1,
     at::Tensor b1, at::Tensor W2, at::Tensor b2);
-bool pair_coord_supported(int64_t H);
+bool pair_coord_supported(int64_t H, int64_t L);
+at::Tensor mfma_gemm_16x16x4_f32(at::Tensor A, at::Tensor B);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("softmax_dropout_forward", &softmax_dropout_forward,
@@ -200,6 +201,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused GELU + dropout backward (recomputes gelu grad)");
   m.def("mfma_gemm_16x16x32", &mfma_gemm_16x16x32,
         "one-wave bf16 MFMA probe (fragment-layout unit test)");
+  m.def("mfma_gemm_16x16x4_f32", &mfma_gemm_16x16x4_f32,
+        "one-wave fp32 MFMA probe (fragment-layout unit test)");
   m.def("flash_attn_forward", &flash_attn_forward,
         "flash attention forward (bf16, D=64) -> (o, lse, seed)");
   m.def("flash_attn_backward", &flash_attn_backward,
@@ -278,5 +281,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("pair_coord_backward", &pair_coord_backward,
         "coordinate head backward -> (dpair, dW1, db1, dW2, db2)");
   m.def("pair_coord_supported", &pair_coord_supported,
-        "coordinate head kernel supports this head count");
+        "coordinate head kernel supports this head count (and, at 64 heads, L)");
 }

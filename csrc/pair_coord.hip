@@ -33,9 +33,14 @@
 //                 hidden layer, so dW1 stays at 64 registers per lane.
 // Padded entries of pair/pair0 (finfo.min, or anything else) are never used:
 // results at pads come from selects, not from multiplications by zero.
+//
+// The above is H = 8 and 16. H = 64 does not fit this register design; the
+// entries below check it the same way and hand it to the fp32-MFMA kernels of
+// pair_coord_h64.hip.
 #include "common.h"
 #include "dispatch.h"
 #include "fold.h"
+#include "pair_coord_h64.h"
 
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
@@ -44,20 +49,6 @@
 #include <vector>
 
 namespace {
-
-constexpr float kRsqrt2 = 0.70710678118654752440f;
-constexpr float kRsqrt2Pi = 0.39894228040143267794f;
-
-__device__ __forceinline__ float gelu_exact(float x) {
-  return 0.5f * x * (1.f + erff(x * kRsqrt2));
-}
-
-// y = gelu(x), dy = gelu'(x)
-__device__ __forceinline__ void gelu_exact_grad(float x, float& y, float& dy) {
-  const float cdf = 0.5f * (1.f + erff(x * kRsqrt2));
-  y = x * cdf;
-  dy = cdf + x * kRsqrt2Pi * expf(-0.5f * x * x);
-}
 
 template <typename T, int NJ>
 __device__ __forceinline__ void load_j(const T* p, float (&f)[NJ]) {
@@ -315,9 +306,6 @@ __global__ void __launch_bounds__(256) pair_coord_dpair_kernel(
   }
 }
 
-// columns of a partials row: dW1 (k-major, H*H) | db1 (H) | dW2 (H) | db2
-static inline int64_t wgrad_cols(int64_t H) { return H * H + 2 * H + 1; }
-
 // Block blockIdx.x owns hidden units [s*KS, (s+1)*KS), s = blockIdx.x % TPP,
 // and the pairs p*256 + tid (+ P*256 ...), p = blockIdx.x / TPP. It writes
 // its own columns of partials row p; the TPP blocks of a row cover it.
@@ -455,8 +443,15 @@ static PairCoordArgs check_pair_coord(
   a.B = pair.size(0);
   a.H = pair.size(1);
   a.L = pair.size(3);
-  TORCH_CHECK(a.H == 8 || a.H == 16, name,
-              ": the kernel serves H = 8 or 16 heads, got ", a.H);
+  TORCH_CHECK(a.H == 8 || a.H == 16 || a.H == 64, name,
+              ": the kernel serves H = 8, 16 or 64 heads, got ", a.H);
+  if (a.H == 64) {
+    TORCH_CHECK(a.L >= 8 && a.L % 8 == 0, name,
+                ": H = 64 needs L a multiple of 8 and >= 8, got L = ", a.L);
+    TORCH_CHECK(aligned16(pair) && aligned16(pair0), name,
+                ": H = 64 needs pair and pair0 16 B-aligned, got addresses ",
+                pair.data_ptr(), " and ", pair0.data_ptr());
+  }
   TORCH_CHECK(a.B * a.L <= 0x7fffffffLL, name, ": B * L = ", a.B * a.L,
               " does not fit 31 bits");
   TORCH_CHECK(coords.device() == pair.device() && coords.dim() == 3 &&
@@ -532,7 +527,10 @@ static inline int row_grid(int64_t n_rows, int G, int block) {
 
 }  // namespace
 
-bool pair_coord_supported(int64_t H) { return H == 8 || H == 16; }
+// L is looked at for H = 64 alone
+bool pair_coord_supported(int64_t H, int64_t L) {
+  return H == 8 || H == 16 || (H == 64 && L >= 8 && L % 8 == 0);
+}
 
 at::Tensor pair_coord_forward(at::Tensor pair, at::Tensor pair0,
                               at::Tensor coords, at::Tensor inv_n,
@@ -543,6 +541,11 @@ at::Tensor pair_coord_forward(at::Tensor pair, at::Tensor pair0,
   auto out = at::empty({a.B, a.L, 3}, coords.options());
   const int64_t n_rows = a.B * a.L;
   if (n_rows == 0) return out;
+  if (a.H == 64) {
+    pair_coord_h64_forward_launch(out, pair, pair0, coords, inv_n, a.pad, W1,
+                                  b1, W2, b2);
+    return out;
+  }
   const int block = 256;
   auto stream = at::cuda::getCurrentCUDAStream();
   DISPATCH_FTYPES(pair.scalar_type(), "pair_coord_forward", {
@@ -576,10 +579,13 @@ std::vector<at::Tensor> pair_coord_backward(
               grad.sizes(), " strides ", grad.strides());
   auto fopts = coords.options();
   auto dpair = at::empty_like(pair);
-  const int64_t C = wgrad_cols(a.H);
+  const int64_t C = pair_coord_wgrad_cols(a.H);
   const int64_t n_rows = a.B * a.L;
   auto fold = n_rows > 0 ? at::empty({C}, fopts) : at::zeros({C}, fopts);
-  if (n_rows > 0) {
+  if (n_rows > 0 && a.H == 64) {
+    pair_coord_h64_backward_launch(dpair, fold, grad, pair, pair0, coords,
+                                   inv_n, a.pad, W1, b1, W2);
+  } else if (n_rows > 0) {
     const bool vec = a.vec && aligned16(dpair);
     const int64_t n_pairs = n_rows * a.L;
     const int block = 256;

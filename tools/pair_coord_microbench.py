@@ -1,18 +1,22 @@
 #!/usr/bin/env python3
 """Time the equivariant coordinate head (PairCoordHead).
 
-bf16, H = 8, at the stress-config shape (B = 32, L = 128) and at L = 256;
-forward alone and forward+backward (gradients to pair, pair0 and the four
-parameters), with a padding mask. Two columns per line:
+bf16, --heads H (8 by default, 64 for Uni-Mol's shape), at the stress-config
+shape (B = 32, L = 128) and at L = 256; forward alone and forward+backward
+(gradients to pair, pair0 and the four parameters), with a padding mask.
+Two columns, timed alternately eager, fused, eager, fused (--rounds 2):
 
   eager   UNICORE_PAIR_COORD_EAGER=1: permute to channel-last, two Linears
           and a GELU over B*L*L rows, the (B, L, L, 3) product, the sum
-  fused   the HIP kernels of csrc/pair_coord.hip
+  fused   the HIP kernels of csrc/pair_coord.hip / csrc/pair_coord_h64.hip
 
 Same process, same box: the columns are directly comparable. GB/s counts
 the fused path's minimum traffic (forward: read pair and pair0; backward:
-read both twice, write dpair and dpair0).
+read both twice, write dpair and dpair0). The last line per shape times
+ops.pair_coord_fwd / ops.pair_coord_bwd alone (the kernels and the fold,
+without the module's torch ops).
 """
+import argparse
 import os
 import sys
 
@@ -20,6 +24,7 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
+from unicore_amd import ops  # noqa: E402
 from unicore_amd.modules import PairCoordHead  # noqa: E402
 
 
@@ -37,8 +42,13 @@ def _time(fn, iters):
 
 
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--heads", type=int, default=8)
+    ap.add_argument("--rounds", type=int, default=2)
+    a = ap.parse_args()
     torch.manual_seed(0)
-    H = 8
+    H = a.heads
+    os.environ["UNICORE_PAIR_COORD_H64"] = "1"
     for B, L in ((32, 128), (32, 256)):
         mask = torch.zeros(B, L, dtype=torch.bool, device="cuda")
         mask[::2, L - 5:] = True
@@ -54,27 +64,44 @@ def main():
         head = PairCoordHead(H).cuda()
         nbytes = pair.numel() * 2
 
-        res = {}
-        for col, gate in (("eager", "1"), ("fused", "0")):
-            os.environ["UNICORE_PAIR_COORD_EAGER"] = gate
+        def fwd():
+            with torch.no_grad():
+                head(pair, pair0, coords, mask)
 
-            def fwd():
-                with torch.no_grad():
-                    head(pair, pair0, coords, mask)
+        def fwd_bwd():
+            pair.grad = pair0.grad = None
+            head.zero_grad(set_to_none=True)
+            head(pair, pair0, coords, mask).backward(grad)
 
-            def fwd_bwd():
-                pair.grad = pair0.grad = None
-                head.zero_grad(set_to_none=True)
-                head(pair, pair0, coords, mask).backward(grad)
-
-            res[col] = (_time(fwd, 50), _time(fwd_bwd, 30))
-        (ef, eb), (ff, fb) = res["eager"], res["fused"]
+        res = {"eager": [], "fused": []}
+        for _ in range(a.rounds):
+            for col, gate in (("eager", "1"), ("fused", "0")):
+                os.environ["UNICORE_PAIR_COORD_EAGER"] = gate
+                res[col].append((_time(fwd, 50), _time(fwd_bwd, 30)))
+        (ef, eb), (ff, fb) = res["eager"][-1], res["fused"][-1]
         print(
             f"pair_coord bf16 B={B} L={L} H={H}: fwd eager {ef:8.1f} us fused "
             f"{ff:7.1f} us (fused {ef / ff:5.2f}x eager, "
             f"{2 * nbytes / ff / 1e3:6.1f} GB/s) | fwd+bwd eager {eb:8.1f} us "
             f"fused {fb:7.1f} us (fused {eb / fb:5.2f}x eager, "
             f"{8 * nbytes / fb / 1e3:6.1f} GB/s)"
+        )
+        for col in ("eager", "fused"):
+            print(f"  {col} rounds, fwd / fwd+bwd us: " + ", ".join(
+                f"{f:.1f} / {b:.1f}" for f, b in res[col]))
+
+        w = [p.detach().float() for p in head.parameters()]
+        w[2] = w[2].view(-1)
+        inv_n = 1.0 / ((~mask).sum(1) - 1).clamp(min=1).float()
+        p, p0 = pair.detach(), pair0.detach()
+        kf = _time(lambda: ops.pair_coord_fwd(p, p0, coords, inv_n, mask, *w), 50)
+        kb = _time(
+            lambda: ops.pair_coord_bwd(grad, p, p0, coords, inv_n, mask, *w), 50)
+        print(
+            f"  kernels alone: fwd {kf:7.1f} us, {2 * nbytes / 1e6:.1f} MB, "
+            f"{2 * nbytes / kf / 1e3:6.1f} GB/s | bwd (dpair + wgrad + fold) "
+            f"{kb:7.1f} us, {5 * nbytes / 1e6:.1f} MB, "
+            f"{5 * nbytes / kb / 1e3:6.1f} GB/s"
         )
 
 

@@ -12,11 +12,13 @@ weighted sum of difference vectors, so it rotates with the input and ignores
 translations.
 
 On GPU this is one HIP kernel forward and two plus the column fold backward
-(csrc/pair_coord.hip): the eager chain's permute to channel-last, its two
-Linears and GELU over B*L*L rows and its (B, L, L, 3) product never exist.
-The eager function below is the definition, the CPU path, the path for head
-counts the kernel does not serve, and what ``UNICORE_PAIR_COORD_EAGER=1``
-selects.
+(csrc/pair_coord.hip at 8 and 16 heads, the fp32-MFMA kernels of
+csrc/pair_coord_h64.hip at 64 heads with L % 8 == 0, gate
+``UNICORE_PAIR_COORD_H64``): the eager chain's permute to channel-last, its
+two Linears and GELU over B*L*L rows and its (B, L, L, 3) product never
+exist. The eager function below is the definition, the CPU path, the path
+for head counts and lengths the kernels do not serve, and what
+``UNICORE_PAIR_COORD_EAGER=1`` selects.
 """
 
 import os
@@ -24,6 +26,14 @@ import os
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+
+# default of the UNICORE_PAIR_COORD_H64 gate (64 heads, the fp32-MFMA kernels
+# of csrc/pair_coord_h64.hip; L % 8 == 0, any other L runs eager): on.
+# Same-box figures (profiles/mol_coord_head_h64.txt): forward+backward of the
+# module at B 32 is 2883 -> 463 us at L 128 and 9201 -> 1495 us at L 256,
+# against a spread of 3.2 / 1.3 us between the repeated eager rounds.
+_PAIR_COORD_H64_DEFAULT = "1"
 
 
 def _real_atoms(B, L, padding_mask, device):
@@ -85,9 +95,12 @@ def pair_coord_fused_ok(pair):
         return False
     if not pair.is_cuda:
         return False
+    if pair.size(1) == 64 and os.environ.get(
+            "UNICORE_PAIR_COORD_H64", _PAIR_COORD_H64_DEFAULT) != "1":
+        return False
     from unicore_amd import ops
 
-    return ops.pair_coord_supported(pair.size(1), pair.dtype)
+    return ops.pair_coord_supported(pair.size(1), pair.dtype, pair.size(2))
 
 
 def pair_coord(pair, pair0, coords, fc1_weight, fc1_bias, fc2_weight,

@@ -381,14 +381,18 @@ def pair_coord_bwd(grad, pair, pair0, coords, inv_n, pad, w1, b1, w2, b2):
     )
 
 
-def pair_coord_supported(H, dtype) -> bool:
+def pair_coord_supported(H, dtype, L=None) -> bool:
     # mirrors the host check in csrc/pair_coord.hip; pure Python so a missing
-    # extension still fails loudly in pair_coord_fwd
+    # extension still fails loudly in pair_coord_fwd. H = 64
+    # (csrc/pair_coord_h64.hip) needs L, a multiple of 8; at 8 and 16 heads L
+    # is not looked at.
     import torch
 
-    return int(H) in (8, 16) and dtype in (
-        torch.float32, torch.float16, torch.bfloat16
-    )
+    if dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        return False
+    if int(H) == 64:
+        return L is not None and int(L) >= 8 and int(L) % 8 == 0
+    return int(H) in (8, 16)
 
 
 def softmax_dropout_bwd_bias(grad, softmax_out, dmask, p, bb, bq, od):
