@@ -3,6 +3,8 @@
 // reference's 8 separate CUDA extensions (reference setup.py:141-387).
 #include <torch/extension.h>
 
+#include "pair_dist_h64.h"
+
 #include <optional>
 #include <vector>
 
@@ -162,6 +164,140 @@ std::vector<at::Tensor> pair_coord_backward(
 bool pair_coord_supported(int64_t H, int64_t L);
 at::Tensor mfma_gemm_16x16x4_f32(at::Tensor A, at::Tensor B);
 
+// ---------------------------------------------------------------------------
+// Pair distance head (pair_dist_h64.hip): the entries and their host checks
+// ---------------------------------------------------------------------------
+
+bool pair_dist_supported(int64_t H, int64_t L) {
+  return H == 64 && L >= 8 && L % 8 == 0;
+}
+
+namespace {
+
+struct PairDistArgs {
+  int64_t B, L;
+  const uint8_t* pad;
+  at::Tensor padc;
+};
+
+PairDistArgs check_pair_dist(const char* name, const at::Tensor& pair,
+                             const std::optional<at::Tensor>& pad,
+                             const at::Tensor& W1, const at::Tensor& b1,
+                             const at::Tensor& gamma, const at::Tensor& beta,
+                             const at::Tensor& w2, const at::Tensor& b2) {
+  TORCH_CHECK(pair.is_cuda(), name, ": pair must be on the GPU, got device ",
+              pair.device());
+  TORCH_CHECK(pair.scalar_type() == at::kFloat ||
+                  pair.scalar_type() == at::kHalf ||
+                  pair.scalar_type() == at::kBFloat16,
+              name, ": pair must be fp32, fp16 or bf16, got ",
+              pair.scalar_type());
+  TORCH_CHECK(pair.dim() == 4 && pair.size(2) == pair.size(3), name,
+              ": pair must be (B, H, L, L), got sizes ", pair.sizes());
+  PairDistArgs a;
+  a.B = pair.size(0);
+  a.L = pair.size(3);
+  TORCH_CHECK(pair.size(1) == 64, name,
+              ": the kernels serve H = 64 heads, got H = ", pair.size(1));
+  TORCH_CHECK(a.L >= 8 && a.L % 8 == 0, name,
+              ": needs L a multiple of 8 and >= 8, got L = ", a.L);
+  TORCH_CHECK(pair.is_contiguous(), name,
+              ": pair must be contiguous, got sizes ", pair.sizes(),
+              " strides ", pair.strides());
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(pair.data_ptr()) % 16 == 0, name,
+              ": pair must be 16 B-aligned, got address ", pair.data_ptr());
+  TORCH_CHECK(a.B * a.L <= 0x7fffffffLL, name, ": B * L = ", a.B * a.L,
+              " does not fit 31 bits");
+  const int64_t tiles = (a.L + 31) / 32;
+  TORCH_CHECK(a.B * tiles * tiles <= 0x7fffffffLL, name, ": a grid of ",
+              a.B * tiles * tiles, " 32 x 32 tiles does not fit 31 bits");
+  a.pad = nullptr;
+  if (pad.has_value()) {
+    TORCH_CHECK(pad->device() == pair.device() &&
+                    pad->scalar_type() == at::kBool && pad->dim() == 2 &&
+                    pad->size(0) == a.B && pad->size(1) == a.L,
+                name, ": padding_mask must be bool (B, L) = (", a.B, ", ", a.L,
+                ") on the device of pair, got ", pad->scalar_type(), " sizes ",
+                pad->sizes(), " on ", pad->device());
+    a.padc = pad->contiguous();
+    // the wgrad kernel reads four pad bytes as one word
+    if (reinterpret_cast<uintptr_t>(a.padc.data_ptr()) % 4 != 0)
+      a.padc = a.padc.clone();
+    a.pad = (const uint8_t*)a.padc.data_ptr<bool>();
+  }
+  auto check_w = [&](const char* wn, const at::Tensor& w,
+                     at::IntArrayRef shape) {
+    TORCH_CHECK(w.device() == pair.device(), name, ": ", wn,
+                " must be on the device of pair, got ", w.device(), " vs ",
+                pair.device());
+    TORCH_CHECK(w.scalar_type() == at::kFloat, name, ": ", wn,
+                " must be fp32, got ", w.scalar_type());
+    TORCH_CHECK(w.sizes() == shape && w.is_contiguous(), name, ": ", wn,
+                " must be contiguous ", shape, ", got sizes ", w.sizes(),
+                " strides ", w.strides());
+  };
+  check_w("dense.weight", W1, {64, 64});
+  check_w("dense.bias", b1, {64});
+  check_w("layer_norm.weight", gamma, {64});
+  check_w("layer_norm.bias", beta, {64});
+  check_w("out_proj.weight", w2, {64});
+  check_w("out_proj.bias", b2, {1});
+  return a;
+}
+
+}  // namespace
+
+// -> dist (B, L, L) fp32, symmetric, 0 where i or j is padded
+at::Tensor pair_dist_forward(at::Tensor pair, std::optional<at::Tensor> pad,
+                             at::Tensor W1, at::Tensor b1, at::Tensor gamma,
+                             at::Tensor beta, at::Tensor w2, at::Tensor b2,
+                             double eps) {
+  const PairDistArgs a = check_pair_dist("pair_dist_forward", pair, pad, W1, b1,
+                                         gamma, beta, w2, b2);
+  auto out = at::empty({a.B, a.L, a.L}, W1.options());
+  if (a.B == 0) return out;
+  auto F = at::empty_like(out);
+  pair_dist_h64_forward_launch(F, pair, a.pad, W1, b1, gamma, beta, w2, b2,
+                               (float)eps);
+  pair_dist_sym_launch(out, F, a.pad);
+  return out;
+}
+
+// -> (dpair, dW1 (64,64), db1, dgamma, dbeta, dw2 (64 each), db2 (1)); the
+// parameter gradients fp32
+std::vector<at::Tensor> pair_dist_backward(
+    at::Tensor grad, at::Tensor pair, std::optional<at::Tensor> pad,
+    at::Tensor W1, at::Tensor b1, at::Tensor gamma, at::Tensor beta,
+    at::Tensor w2, at::Tensor b2, double eps) {
+  const PairDistArgs a = check_pair_dist("pair_dist_backward", pair, pad, W1,
+                                         b1, gamma, beta, w2, b2);
+  TORCH_CHECK(grad.device() == pair.device() &&
+                  grad.scalar_type() == at::kFloat && grad.dim() == 3 &&
+                  grad.size(0) == a.B && grad.size(1) == a.L &&
+                  grad.size(2) == a.L && grad.is_contiguous(),
+              "pair_dist_backward: grad must be contiguous fp32 (B, L, L) = (",
+              a.B, ", ", a.L, ", ", a.L, ") on the device of pair, got ",
+              grad.scalar_type(), " sizes ", grad.sizes(), " strides ",
+              grad.strides(), " on ", grad.device());
+  auto dpair = at::empty_like(pair);
+  const int64_t C = pair_dist_h64_wgrad_cols();
+  auto fold = a.B > 0 ? at::empty({C}, W1.options()) : at::zeros({C}, W1.options());
+  if (a.B > 0) {
+    auto dF = at::empty_like(grad);
+    pair_dist_sym_launch(dF, grad, a.pad);
+    pair_dist_h64_backward_launch(dpair, fold, dF, pair, a.pad, W1, b1, gamma,
+                                  beta, w2, (float)eps);
+  }
+  const int64_t H = 64, HH = H * H;
+  return {dpair,
+          fold.narrow(0, 0, HH).view({H, H}),
+          fold.narrow(0, HH, H),
+          fold.narrow(0, HH + H, H),
+          fold.narrow(0, HH + 2 * H, H),
+          fold.narrow(0, HH + 3 * H, H),
+          fold.narrow(0, HH + 4 * H, 1)};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("softmax_dropout_forward", &softmax_dropout_forward,
         "fused softmax(+mask,+bias)+dropout forward (gfx950)");
@@ -282,4 +418,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "coordinate head backward -> (dpair, dW1, db1, dW2, db2)");
   m.def("pair_coord_supported", &pair_coord_supported,
         "coordinate head kernel supports this head count (and, at 64 heads, L)");
+  m.def("pair_dist_forward", &pair_dist_forward,
+        "pair distance head: (B,64,L,L) pair track -> (B,L,L) fp32 distances");
+  m.def("pair_dist_backward", &pair_dist_backward,
+        "distance head backward -> (dpair, dW1, db1, dgamma, dbeta, dw2, db2)");
+  m.def("pair_dist_supported", &pair_dist_supported,
+        "distance head kernels serve this head count and L");
 }

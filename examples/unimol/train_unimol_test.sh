@@ -5,6 +5,10 @@
 # Pair track + SE(3)-equivariant coordinate head (Uni-Mol's own head): pass
 # the flag after the GPU count,
 #   bash train_unimol_test.sh 8 --coord-head equivariant
+# Uni-Mol's pairwise distance head and masked distance loss on top of it
+# (fused kernels at 64 heads):
+#   bash train_unimol_test.sh 8 --coord-head equivariant \
+#     --encoder-attention-heads 64 --dist-head --dist-loss-weight 1
 set -e
 n_gpu=${1:-8}
 exec python -m torch.distributed.run --nnodes=1 --nproc-per-node "$n_gpu" \

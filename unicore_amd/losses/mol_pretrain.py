@@ -6,10 +6,15 @@ coordinate deltas (the Uni-Mol pretraining recipe shape)."""
 import math
 
 import torch
+import torch.nn.functional as F
 
 from unicore_amd import metrics
 from unicore_amd.losses import UnicoreLoss, register_loss
 from unicore_amd.modules.cross_entropy import fused_nll_loss
+
+# Uni-Mol's normalisation of interatomic distances (Angstrom)
+DIST_MEAN = 6.312
+DIST_STD = 3.379
 
 
 @register_loss("mol_pretrain")
@@ -18,12 +23,34 @@ class MolPretrainLoss(UnicoreLoss):
         super().__init__(task)
         self.padding_idx = task.dictionary.pad()
         self.coord_loss_weight = getattr(task.args, "coord_loss_weight", 1.0)
+        self.dist_loss_weight = getattr(task.args, "dist_loss_weight", 0.0)
+
+    def dist_loss(self, dist, sample, masked):
+        """Uni-Mol's masked distance loss: smooth L1 (sum) between the
+        predicted and the normalised clean distances over pairs whose row is
+        a masked atom and whose column is a real atom."""
+        net = sample["net_input"]
+        clean = net["src_coord"].float() + sample["coord_target"].float()
+        length = (clean.unsqueeze(1) - clean.unsqueeze(2)).norm(dim=-1)
+        target = (length - DIST_MEAN) / DIST_STD
+        real = net["src_tokens"].ne(self.padding_idx)
+        sel = masked.unsqueeze(2) & real.unsqueeze(1)
+        return F.smooth_l1_loss(dist[sel].float(), target[sel], beta=1.0,
+                                reduction="sum")
 
     def forward(self, model, sample, reduce=True):
-        logits, coord_delta = model(**sample["net_input"])
+        net_output = model(**sample["net_input"])
+        logits, coord_delta = net_output[0], net_output[1]
+        if self.dist_loss_weight > 0 and len(net_output) < 3:
+            raise ValueError(
+                f"--dist-loss-weight {self.dist_loss_weight} needs a model "
+                "that returns distances (mol_pairbias with --coord-head "
+                f"equivariant --dist-head), got {len(net_output)} outputs"
+            )
         target = sample["target"]
         masked = target.ne(self.padding_idx)
         sample_size = masked.int().sum()
+        masked_atoms = masked
         masked = torch.where(masked.any(), masked, masked.new([True]))
         token_loss = fused_nll_loss(logits[masked], target[masked], ignore_index=self.padding_idx)
         # coordinate denoising: predict the delta back to clean positions
@@ -40,6 +67,11 @@ class MolPretrainLoss(UnicoreLoss):
             "sample_size": sample_size,
             "seq_len": target.size(1) * target.size(0),
         }
+        if self.dist_loss_weight > 0:
+            dist_loss = self.dist_loss(net_output[2], sample, masked_atoms)
+            loss = loss + self.dist_loss_weight * dist_loss
+            logging_output["loss"] = loss.data
+            logging_output["dist_loss"] = dist_loss.data
         return loss, sample_size, logging_output
 
     @staticmethod
@@ -57,6 +89,10 @@ class MolPretrainLoss(UnicoreLoss):
             "token_loss", token_sum / denom / math.log(2), sample_size, round=3
         )
         metrics.log_scalar("coord_loss", coord_sum / denom, sample_size, round=3)
+        if any("dist_loss" in log for log in logging_outputs):
+            dist_sum = sum(log.get("dist_loss", 0) for log in logging_outputs)
+            metrics.log_scalar("dist_loss", dist_sum / denom, sample_size,
+                               round=3)
 
     @staticmethod
     def logging_outputs_can_be_summed(is_train) -> bool:

@@ -25,6 +25,7 @@ from unicore_amd.models import (
 )
 from unicore_amd.modules import (
     PairCoordHead,
+    PairDistHead,
     RMSNorm,
     SelfMultiheadAttention,
     dropout_add,
@@ -170,6 +171,12 @@ class MolPairBiasModel(BaseUnicoreModel):
             "carry the attention logits through the layers as a pair track "
             "and read the coordinate update off it (PairCoordHead)",
         )
+        parser.add_argument(
+            "--dist-head", action="store_true",
+            help="also predict the (B, L, L) pairwise distances from the "
+            "final pair track (PairDistHead, Uni-Mol's DistanceHead); needs "
+            "--coord-head equivariant",
+        )
 
     def __init__(self, args, dictionary):
         super().__init__()
@@ -203,6 +210,14 @@ class MolPairBiasModel(BaseUnicoreModel):
             self.coord_head = PairCoordHead(args.encoder_attention_heads)
         else:
             self.coord_head = nn.Linear(E, 3)
+        self.with_dist = bool(args.dist_head)
+        if self.with_dist:
+            if not self.equivariant:
+                raise ValueError(
+                    "--dist-head reads the pair track: it needs --coord-head "
+                    f"equivariant, got --coord-head {args.coord_head}"
+                )
+            self.dist_head = PairDistHead(args.encoder_attention_heads)
         self.apply(init_bert_params)
 
     @classmethod
@@ -219,9 +234,10 @@ class MolPairBiasModel(BaseUnicoreModel):
             pair = bias
             for layer in self.layers:
                 x, pair = layer(x, pair, padding_mask, return_pair=True)
-            coord_delta = self.coord_head(
-                pair.contiguous(), bias, src_coord, padding_mask
-            )
+            pair = pair.contiguous()
+            coord_delta = self.coord_head(pair, bias, src_coord, padding_mask)
+            if self.with_dist:
+                dist = self.dist_head(pair, padding_mask)
         else:
             for layer in self.layers:
                 x = layer(x, bias, padding_mask)
@@ -229,6 +245,8 @@ class MolPairBiasModel(BaseUnicoreModel):
         logits = self.lm_head(x)
         if not self.equivariant:
             coord_delta = self.coord_head(x)
+        if self.with_dist:
+            return logits, coord_delta.float(), dist
         return logits, coord_delta.float()
 
 
@@ -244,3 +262,4 @@ def base_mol_architecture(args):
     args.activation_dropout = getattr(args, "activation_dropout", 0.0)
     args.max_seq_len = getattr(args, "max_seq_len", 512)
     args.coord_head = getattr(args, "coord_head", "linear")
+    args.dist_head = getattr(args, "dist_head", False)

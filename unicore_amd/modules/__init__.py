@@ -7,6 +7,7 @@ from .gelu_dropout import gelu_dropout
 from .dropout_add import dropout_add
 from .gaussian import gaussian_basis
 from .pair_coord import PairCoordHead, pair_coord
+from .pair_dist import PairDistHead, pair_dist
 from .gated_mul import gated_mul
 from .triangle import triangle_multiply
 from .outer_product import outer_product_mean

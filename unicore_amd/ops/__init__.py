@@ -395,6 +395,35 @@ def pair_coord_supported(H, dtype, L=None) -> bool:
     return int(H) in (8, 16)
 
 
+def pair_dist_fwd(pair, pad, w1, b1, gamma, beta, w2, b2, eps):
+    """Pair distance head: pair (B,64,L,L) contiguous, pad (B,L) bool or
+    None, fp32 dense (64,64)/(64), LayerNorm (64)/(64) and out_proj (64)/(1)
+    parameters -> (B,L,L) fp32 symmetric distances. csrc/pair_dist_h64.hip."""
+    require_kernels()
+    return _kernels.pair_dist_forward(
+        pair, pad, w1, b1, gamma, beta, w2, b2, float(eps)
+    )
+
+
+def pair_dist_bwd(grad, pair, pad, w1, b1, gamma, beta, w2, b2, eps):
+    """-> (dpair in the dtype of pair, dW1 (64,64), db1, dgamma, dbeta, dw2
+    (64 each), db2 (1)), the parameter gradients fp32 and deterministic."""
+    require_kernels()
+    return _kernels.pair_dist_backward(
+        grad, pair, pad, w1, b1, gamma, beta, w2, b2, float(eps)
+    )
+
+
+def pair_dist_supported(H, dtype, L) -> bool:
+    # mirrors the host check in csrc/bindings.cpp; pure Python so a missing
+    # extension still fails loudly in pair_dist_fwd
+    import torch
+
+    if dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        return False
+    return int(H) == 64 and L is not None and int(L) >= 8 and int(L) % 8 == 0
+
+
 def softmax_dropout_bwd_bias(grad, softmax_out, dmask, p, bb, bq, od):
     """In-place softmax backward that also returns the broadcast bias grad
     (fp32, (bb*bq, k)) without re-reading the grad tensor."""

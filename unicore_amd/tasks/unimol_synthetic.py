@@ -98,6 +98,9 @@ class UniMolSyntheticTask(UnicoreTask):
         parser.add_argument("--mask-prob", default=0.15, type=float)
         parser.add_argument("--coord-noise-std", default=0.3, type=float)
         parser.add_argument("--coord-loss-weight", default=1.0, type=float)
+        parser.add_argument("--dist-loss-weight", default=0.0, type=float,
+                            help="weight of the masked distance loss; needs "
+                            "a model that predicts distances (--dist-head)")
 
     def __init__(self, args, dictionary):
         super().__init__(args)
