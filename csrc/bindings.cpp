@@ -4,6 +4,7 @@
 #include <torch/extension.h>
 
 #include "pair_dist_h64.h"
+#include "pair_gauss_h64.h"
 
 #include <optional>
 #include <vector>
@@ -298,6 +299,143 @@ std::vector<at::Tensor> pair_dist_backward(
           fold.narrow(0, HH + 4 * H, 1)};
 }
 
+// ---------------------------------------------------------------------------
+// Uni-Mol pair embedding (pair_gauss_h64.hip): the entries and their host
+// checks
+// ---------------------------------------------------------------------------
+
+bool pair_gauss_supported(int64_t K, int64_t H, int64_t L) {
+  return K == 128 && H == 64 && L >= 8 && L % 8 == 0;
+}
+
+namespace {
+
+struct PairGaussArgs {
+  int64_t B, L;
+  const uint8_t* pad;
+  at::Tensor padc;
+};
+
+PairGaussArgs check_pair_gauss(const char* name, const at::Tensor& coords,
+                               const at::Tensor& a, const at::Tensor& b,
+                               const std::optional<at::Tensor>& pad,
+                               const at::Tensor& means, const at::Tensor& stds,
+                               const at::Tensor& W1, const at::Tensor& b1,
+                               const at::Tensor& W2, const at::Tensor* b2) {
+  TORCH_CHECK(coords.is_cuda(), name, ": coords must be on the GPU, got device ",
+              coords.device());
+  TORCH_CHECK(coords.scalar_type() == at::kFloat && coords.dim() == 3 &&
+                  coords.size(2) == 3 && coords.is_contiguous(),
+              name, ": coords must be contiguous fp32 (B, L, 3), got ",
+              coords.scalar_type(), " sizes ", coords.sizes(), " strides ",
+              coords.strides());
+  PairGaussArgs r;
+  r.B = coords.size(0);
+  r.L = coords.size(1);
+  TORCH_CHECK(W1.scalar_type() == at::kBFloat16, name,
+              ": the kernels serve a bf16 module, got linear1.weight in ",
+              W1.scalar_type());
+  TORCH_CHECK(means.dim() == 1 && means.size(0) == 128, name,
+              ": the kernels serve K = 128 gaussians, got means of sizes ",
+              means.sizes());
+  TORCH_CHECK(W2.dim() == 2 && W2.size(0) == 64, name,
+              ": the kernels serve H = 64 heads, got linear2.weight of sizes ",
+              W2.sizes());
+  TORCH_CHECK(r.L >= 8 && r.L % 8 == 0, name,
+              ": needs L a multiple of 8 and >= 8, got L = ", r.L);
+  TORCH_CHECK(r.B * r.L <= 0x7fffffffLL, name, ": B * L = ", r.B * r.L,
+              " does not fit 31 bits");
+  auto check_t = [&](const char* tn, const at::Tensor& t, at::ScalarType st,
+                     at::IntArrayRef shape) {
+    TORCH_CHECK(t.device() == coords.device(), name, ": ", tn,
+                " must be on the device of coords, got ", t.device(), " vs ",
+                coords.device());
+    TORCH_CHECK(t.scalar_type() == st, name, ": ", tn, " must be ", st,
+                ", got ", t.scalar_type());
+    TORCH_CHECK(t.sizes() == shape && t.is_contiguous(), name, ": ", tn,
+                " must be contiguous ", shape, ", got sizes ", t.sizes(),
+                " strides ", t.strides());
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name,
+                ": ", tn, " must be 16 B-aligned, got address ", t.data_ptr());
+  };
+  check_t("a", a, at::kFloat, {r.B, r.L, r.L});
+  check_t("b", b, at::kFloat, {r.B, r.L, r.L});
+  check_t("means", means, at::kFloat, {128});
+  check_t("stds", stds, at::kFloat, {128});
+  check_t("linear1.weight", W1, at::kBFloat16, {128, 128});
+  check_t("linear1.bias", b1, at::kBFloat16, {128});
+  check_t("linear2.weight", W2, at::kBFloat16, {64, 128});
+  if (b2 != nullptr) check_t("linear2.bias", *b2, at::kBFloat16, {64});
+  r.pad = nullptr;
+  if (pad.has_value()) {
+    TORCH_CHECK(pad->device() == coords.device() &&
+                    pad->scalar_type() == at::kBool && pad->dim() == 2 &&
+                    pad->size(0) == r.B && pad->size(1) == r.L,
+                name, ": padding_mask must be bool (B, L) = (", r.B, ", ", r.L,
+                ") on the device of coords, got ", pad->scalar_type(),
+                " sizes ", pad->sizes(), " on ", pad->device());
+    r.padc = pad->contiguous();
+    // the backward kernels read eight pad bytes as one word
+    if (reinterpret_cast<uintptr_t>(r.padc.data_ptr()) % 8 != 0)
+      r.padc = r.padc.clone();
+    r.pad = (const uint8_t*)r.padc.data_ptr<bool>();
+  }
+  return r;
+}
+
+}  // namespace
+
+// -> (B, 64, L, L) bf16, fill at padded keys
+at::Tensor pair_gauss_forward(at::Tensor coords, at::Tensor a, at::Tensor b,
+                              std::optional<at::Tensor> pad, at::Tensor means,
+                              at::Tensor stds, at::Tensor W1, at::Tensor b1,
+                              at::Tensor W2, at::Tensor b2, double fill) {
+  const PairGaussArgs r = check_pair_gauss("pair_gauss_forward", coords, a, b,
+                                           pad, means, stds, W1, b1, W2, &b2);
+  auto out = at::empty({r.B, 64, r.L, r.L}, W1.options());
+  if (r.B == 0) return out;
+  pair_gauss_h64_forward_launch(out, coords, a, b, r.pad, means, stds, W1, b1,
+                                W2, b2, (float)fill);
+  return out;
+}
+
+// -> (d_a, d_b (B, L, L), d_means, d_stds (128), dW1 (128,128), db1 (128),
+// dW2 (64,128), db2 (64)), all fp32
+std::vector<at::Tensor> pair_gauss_backward(
+    at::Tensor grad, at::Tensor coords, at::Tensor a, at::Tensor b,
+    std::optional<at::Tensor> pad, at::Tensor means, at::Tensor stds,
+    at::Tensor W1, at::Tensor b1, at::Tensor W2) {
+  const PairGaussArgs r = check_pair_gauss("pair_gauss_backward", coords, a, b,
+                                           pad, means, stds, W1, b1, W2,
+                                           nullptr);
+  TORCH_CHECK(grad.device() == coords.device() &&
+                  grad.scalar_type() == at::kBFloat16 && grad.dim() == 4 &&
+                  grad.size(0) == r.B && grad.size(1) == 64 &&
+                  grad.size(2) == r.L && grad.size(3) == r.L &&
+                  grad.is_contiguous() &&
+                  reinterpret_cast<uintptr_t>(grad.data_ptr()) % 16 == 0,
+              "pair_gauss_backward: grad must be contiguous, 16 B-aligned bf16 "
+              "(B, 64, L, L) = (", r.B, ", 64, ", r.L, ", ", r.L,
+              ") on the device of coords, got ", grad.scalar_type(), " sizes ",
+              grad.sizes(), " strides ", grad.strides(), " on ", grad.device());
+  const int64_t K = 128, H = 64, C = pair_gauss_h64_wgrad_cols();
+  auto d_a = at::empty_like(a);
+  auto d_b = at::empty_like(b);
+  auto sf = r.B > 0 ? at::empty({2 * K}, a.options()) : at::zeros({2 * K}, a.options());
+  auto wf = r.B > 0 ? at::empty({C}, a.options()) : at::zeros({C}, a.options());
+  if (r.B > 0)
+    pair_gauss_h64_backward_launch(d_a, d_b, sf, wf, grad, coords, a, b, r.pad,
+                                   means, stds, W1, b1, W2);
+  return {d_a,
+          d_b,
+          sf.narrow(0, 0, K),
+          sf.narrow(0, K, K),
+          wf.narrow(0, 0, K * K).view({K, K}),
+          wf.narrow(0, K * K, K),
+          wf.narrow(0, K * K + K, H * K).view({H, K}),
+          wf.narrow(0, K * K + K + H * K, H)};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("softmax_dropout_forward", &softmax_dropout_forward,
         "fused softmax(+mask,+bias)+dropout forward (gfx950)");
@@ -422,6 +560,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "pair distance head: (B,64,L,L) pair track -> (B,L,L) fp32 distances");
   m.def("pair_dist_backward", &pair_dist_backward,
         "distance head backward -> (dpair, dW1, db1, dgamma, dbeta, dw2, db2)");
+  m.def("pair_gauss_forward", &pair_gauss_forward,
+        "Uni-Mol pair embedding forward, K = 128, H = 64, bf16 (gfx950)");
+  m.def("pair_gauss_backward", &pair_gauss_backward,
+        "Uni-Mol pair embedding backward: d_a, d_b and the parameter gradients");
+  m.def("pair_gauss_supported", &pair_gauss_supported,
+        "pair embedding kernels serve this (K, H, L)");
   m.def("pair_dist_supported", &pair_dist_supported,
         "distance head kernels serve this head count and L");
 }

@@ -26,6 +26,7 @@ from unicore_amd.models import (
 from unicore_amd.modules import (
     PairCoordHead,
     PairDistHead,
+    PairGaussianEmbed,
     RMSNorm,
     SelfMultiheadAttention,
     dropout_add,
@@ -177,6 +178,13 @@ class MolPairBiasModel(BaseUnicoreModel):
             "final pair track (PairDistHead, Uni-Mol's DistanceHead); needs "
             "--coord-head equivariant",
         )
+        parser.add_argument(
+            "--pair-embed", choices=["linear", "unimol"],
+            help="linear: gaussians of the distance and one Linear K -> heads "
+            "(GaussianPairBias); unimol: Uni-Mol's embedding, an affine map of "
+            "the distance per atom-type pair, normalised gaussians and a "
+            "K -> K -> heads MLP (PairGaussianEmbed)",
+        )
 
     def __init__(self, args, dictionary):
         super().__init__()
@@ -185,9 +193,16 @@ class MolPairBiasModel(BaseUnicoreModel):
         self.padding_idx = dictionary.pad()
         E = args.encoder_embed_dim
         self.embed_tokens = Embedding(len(dictionary), E, self.padding_idx)
-        self.pair_bias = GaussianPairBias(
-            args.gaussian_kernels, args.encoder_attention_heads
-        )
+        self.unimol_embed = args.pair_embed == "unimol"
+        if self.unimol_embed:
+            self.pair_bias = PairGaussianEmbed(
+                args.gaussian_kernels, args.encoder_attention_heads,
+                len(dictionary),
+            )
+        else:
+            self.pair_bias = GaussianPairBias(
+                args.gaussian_kernels, args.encoder_attention_heads
+            )
         self.layers = nn.ModuleList(
             [
                 PairBiasEncoderLayer(
@@ -227,7 +242,10 @@ class MolPairBiasModel(BaseUnicoreModel):
     def forward(self, src_tokens, src_coord, **kwargs):
         padding_mask = src_tokens.eq(self.padding_idx)
         x = self.embed_tokens(src_tokens)
-        bias = self.pair_bias(src_coord, padding_mask)
+        if self.unimol_embed:
+            bias = self.pair_bias(src_coord, src_tokens, padding_mask)
+        else:
+            bias = self.pair_bias(src_coord, padding_mask)
         if self.equivariant:
             # pair track: each layer's attention logits are the next layer's
             # bias; the head reads the update off last logits - first bias
@@ -263,3 +281,4 @@ def base_mol_architecture(args):
     args.max_seq_len = getattr(args, "max_seq_len", 512)
     args.coord_head = getattr(args, "coord_head", "linear")
     args.dist_head = getattr(args, "dist_head", False)
+    args.pair_embed = getattr(args, "pair_embed", "linear")

@@ -424,6 +424,37 @@ def pair_dist_supported(H, dtype, L) -> bool:
     return int(H) == 64 and L is not None and int(L) >= 8 and int(L) % 8 == 0
 
 
+def pair_gauss_fwd(coords, a, b, pad, means, stds, w1, b1, w2, b2, fill):
+    """Uni-Mol pair embedding: coords (B,L,3) fp32, a / b (B,L,L) fp32 (the
+    per-edge-type mul and bias), pad (B,L) bool or None, means / stds (128)
+    fp32, bf16 linear1 (128,128)/(128) and linear2 (64,128)/(64) ->
+    (B,64,L,L) bf16, ``fill`` at padded keys. csrc/pair_gauss_h64.hip."""
+    require_kernels()
+    return _kernels.pair_gauss_forward(
+        coords, a, b, pad, means, stds, w1, b1, w2, b2, float(fill)
+    )
+
+
+def pair_gauss_bwd(grad, coords, a, b, pad, means, stds, w1, b1, w2):
+    """-> (d_a, d_b (B,L,L), d_means, d_stds (128), dW1 (128,128), db1 (128),
+    dW2 (64,128), db2 (64)), all fp32 and deterministic."""
+    require_kernels()
+    return _kernels.pair_gauss_backward(
+        grad, coords, a, b, pad, means, stds, w1, b1, w2
+    )
+
+
+def pair_gauss_supported(K, H, dtype, L) -> bool:
+    # mirrors the host check in csrc/bindings.cpp; pure Python so a missing
+    # extension still fails loudly in pair_gauss_fwd
+    import torch
+
+    return (
+        int(K) == 128 and int(H) == 64 and dtype == torch.bfloat16
+        and L is not None and int(L) >= 8 and int(L) % 8 == 0
+    )
+
+
 def softmax_dropout_bwd_bias(grad, softmax_out, dmask, p, bb, bq, od):
     """In-place softmax backward that also returns the broadcast bias grad
     (fp32, (bb*bq, k)) without re-reading the grad tensor."""
