@@ -5,6 +5,7 @@
 
 #include "pair_dist_h64.h"
 #include "pair_gauss_h64.h"
+#include "pair_norm.h"
 
 #include <optional>
 #include <vector>
@@ -436,6 +437,150 @@ std::vector<at::Tensor> pair_gauss_backward(
           wf.narrow(0, K * K + K + H * K, H)};
 }
 
+// ---------------------------------------------------------------------------
+// Uni-Mol norm regularisers (pair_norm.hip): the entries and their host
+// checks
+// ---------------------------------------------------------------------------
+
+bool pair_norm_supported(int64_t H, int64_t L) {
+  return H >= 4 && H % 4 == 0 && L >= 8 && L % 8 == 0;
+}
+
+namespace {
+
+struct NormPad {
+  const uint8_t* ptr = nullptr;
+  at::Tensor keep;
+};
+
+// bool mask of `shape` on the device of ref; the pair kernel reads eight pad
+// bytes as one word
+NormPad check_norm_pad(const char* name, const std::optional<at::Tensor>& pad,
+                       const at::Tensor& ref, at::IntArrayRef shape) {
+  NormPad r;
+  if (!pad.has_value()) return r;
+  TORCH_CHECK(pad->device() == ref.device() &&
+                  pad->scalar_type() == at::kBool && pad->sizes() == shape,
+              name, ": padding_mask must be bool ", shape,
+              " on the device of the input, got ", pad->scalar_type(),
+              " sizes ", pad->sizes(), " on ", pad->device());
+  r.keep = pad->contiguous();
+  if (reinterpret_cast<uintptr_t>(r.keep.data_ptr()) % 8 != 0)
+    r.keep = r.keep.clone();
+  r.ptr = (const uint8_t*)r.keep.data_ptr<bool>();
+  return r;
+}
+
+void check_norm_tensor(const char* name, const char* tn, const at::Tensor& t) {
+  TORCH_CHECK(t.is_cuda(), name, ": ", tn, " must be on the GPU, got device ",
+              t.device());
+  TORCH_CHECK(t.scalar_type() == at::kFloat ||
+                  t.scalar_type() == at::kBFloat16,
+              name, ": ", tn, " must be fp32 or bf16, got ", t.scalar_type());
+  TORCH_CHECK(t.is_contiguous(), name, ": ", tn,
+              " must be contiguous, got sizes ", t.sizes(), " strides ",
+              t.strides());
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name, ": ",
+              tn, " must be 16 B-aligned, got address ", t.data_ptr());
+}
+
+void check_norm_f32(const char* name, const char* tn, const at::Tensor& t,
+                    const at::Tensor& ref, at::IntArrayRef shape) {
+  TORCH_CHECK(t.device() == ref.device() && t.scalar_type() == at::kFloat &&
+                  t.sizes() == shape && t.is_contiguous() &&
+                  reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+              name, ": ", tn, " must be contiguous, 16 B-aligned fp32 ", shape,
+              " on the device of the input, got ", t.scalar_type(), " sizes ",
+              t.sizes(), " strides ", t.strides(), " on ", t.device());
+}
+
+void check_pair_norm(const char* name, const at::Tensor& pair,
+                     const at::Tensor& bias) {
+  check_norm_tensor(name, "pair", pair);
+  TORCH_CHECK(pair.dim() == 4 && pair.size(2) == pair.size(3), name,
+              ": pair must be (B, H, L, L), got sizes ", pair.sizes());
+  TORCH_CHECK(bias.sizes() == pair.sizes(), name,
+              ": pair and bias must have one shape, got pair ", pair.sizes(),
+              " and bias ", bias.sizes());
+  TORCH_CHECK(bias.scalar_type() == pair.scalar_type() &&
+                  bias.device() == pair.device(),
+              name, ": pair and bias must have one dtype and device, got ",
+              pair.scalar_type(), " on ", pair.device(), " and ",
+              bias.scalar_type(), " on ", bias.device());
+  check_norm_tensor(name, "bias", bias);
+  const int64_t H = pair.size(1), L = pair.size(3);
+  TORCH_CHECK(H >= 4 && H % 4 == 0, name,
+              ": needs H a multiple of 4 and >= 4, got H = ", H);
+  TORCH_CHECK(L >= 8 && L % 8 == 0, name,
+              ": needs L a multiple of 8 and >= 8, got L = ", L);
+  // the kernels index 8-position units with 32 bits
+  const int64_t units = pair.size(0) * H * L * (L / 8);
+  TORCH_CHECK(units <= 0x7fffff00LL, name, ": B * H * L * L / 8 = ", units,
+              " units do not fit 31 bits");
+}
+
+void check_row_norm(const char* name, const at::Tensor& x) {
+  check_norm_tensor(name, "x", x);
+  TORCH_CHECK(x.dim() == 2, name, ": x must be (N, E), got sizes ", x.sizes());
+  const int64_t E = x.size(1);
+  TORCH_CHECK(E >= 8 && E % 8 == 0 && E <= kRowNormMaxE, name,
+              ": needs E a multiple of 8 in [8, ", kRowNormMaxE,
+              "], got E = ", E);
+}
+
+}  // namespace
+
+// -> (coef (B, L, L), rowerr (B, L)), fp32; 0 where i or j is padded
+std::vector<at::Tensor> pair_norm_forward(at::Tensor pair, at::Tensor bias,
+                                          std::optional<at::Tensor> pad) {
+  check_pair_norm("pair_norm_forward", pair, bias);
+  const int64_t B = pair.size(0), L = pair.size(3);
+  const NormPad p = check_norm_pad("pair_norm_forward", pad, pair, {B, L});
+  const auto f32 = pair.options().dtype(at::kFloat);
+  auto coef = at::empty({B, L, L}, f32);
+  auto uerr = at::empty({B, L, L / 8}, f32);
+  if (B > 0) pair_norm_forward_launch(coef, uerr, pair, bias, p.ptr);
+  return {coef, uerr.sum(-1)};
+}
+
+// -> (d_pair, d_bias = -d_pair), as pair
+std::vector<at::Tensor> pair_norm_backward(at::Tensor gscale, at::Tensor coef,
+                                           at::Tensor pair, at::Tensor bias) {
+  check_pair_norm("pair_norm_backward", pair, bias);
+  const int64_t B = pair.size(0), L = pair.size(3);
+  check_norm_f32("pair_norm_backward", "gscale", gscale, pair, {B});
+  check_norm_f32("pair_norm_backward", "coef", coef, pair, {B, L, L});
+  auto d_pair = at::empty_like(pair);
+  auto d_bias = at::empty_like(pair);
+  if (B > 0)
+    pair_norm_backward_launch(d_pair, d_bias, gscale, coef, pair, bias);
+  return {d_pair, d_bias};
+}
+
+// x (N, E) -> (coef (N), err (N)), fp32; 0 at padded rows
+std::vector<at::Tensor> row_norm_forward(at::Tensor x,
+                                         std::optional<at::Tensor> pad) {
+  check_row_norm("row_norm_forward", x);
+  const int64_t N = x.size(0);
+  const NormPad p = check_norm_pad("row_norm_forward", pad, x, {N});
+  const auto f32 = x.options().dtype(at::kFloat);
+  auto coef = at::empty({N}, f32);
+  auto err = at::empty({N}, f32);
+  if (N > 0) row_norm_forward_launch(coef, err, x, p.ptr);
+  return {coef, err};
+}
+
+// -> dx = g_row[n] * coef[n] * x, as x
+at::Tensor row_norm_backward(at::Tensor g_row, at::Tensor coef, at::Tensor x) {
+  check_row_norm("row_norm_backward", x);
+  const int64_t N = x.size(0);
+  check_norm_f32("row_norm_backward", "g_row", g_row, x, {N});
+  check_norm_f32("row_norm_backward", "coef", coef, x, {N});
+  auto dx = at::empty_like(x);
+  if (N > 0) row_norm_backward_launch(dx, g_row, coef, x);
+  return dx;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("softmax_dropout_forward", &softmax_dropout_forward,
         "fused softmax(+mask,+bias)+dropout forward (gfx950)");
@@ -568,4 +713,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "pair embedding kernels serve this (K, H, L)");
   m.def("pair_dist_supported", &pair_dist_supported,
         "distance head kernels serve this head count and L");
+  m.def("pair_norm_forward", &pair_norm_forward,
+        "pair norm regulariser: (B,H,L,L) pair, bias -> (coef (B,L,L), rowerr (B,L))");
+  m.def("pair_norm_backward", &pair_norm_backward,
+        "pair norm regulariser backward -> (d_pair, d_bias = -d_pair)");
+  m.def("pair_norm_supported", &pair_norm_supported,
+        "pair norm kernels serve this head count and L");
+  m.def("row_norm_forward", &row_norm_forward,
+        "row norm regulariser: (N,E) -> (coef (N), err (N))");
+  m.def("row_norm_backward", &row_norm_backward,
+        "row norm regulariser backward -> dx");
 }

@@ -9,6 +9,9 @@
 # (fused kernels at 64 heads):
 #   bash train_unimol_test.sh 8 --coord-head equivariant \
 #     --encoder-attention-heads 64 --dist-head --dist-loss-weight 1
+# Uni-Mol's norm regularisers on the atom representation and on the pair
+# track's update (fused kernels; the second needs the equivariant head):
+#   ... --x-norm-loss 0.01 --delta-pair-repr-norm-loss 0.01
 set -e
 n_gpu=${1:-8}
 exec python -m torch.distributed.run --nnodes=1 --nproc-per-node "$n_gpu" \

@@ -44,6 +44,7 @@ HIP_SOURCES = [
     "csrc/pair_coord_h64.hip",
     "csrc/pair_dist_h64.hip",
     "csrc/pair_gauss_h64.hip",
+    "csrc/pair_norm.hip",
     "csrc/pair_attn.hip",
     "csrc/pair_attn_d8.hip",
 ]

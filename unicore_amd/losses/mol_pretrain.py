@@ -24,6 +24,15 @@ class MolPretrainLoss(UnicoreLoss):
         self.padding_idx = task.dictionary.pad()
         self.coord_loss_weight = getattr(task.args, "coord_loss_weight", 1.0)
         self.dist_loss_weight = getattr(task.args, "dist_loss_weight", 0.0)
+        # Uni-Mol's norm regularisers: (weight, flag, key in the model's
+        # trailing dict, logged name)
+        self.norm_terms = [
+            (getattr(task.args, "x_norm_loss", 0.0) or 0.0, "--x-norm-loss",
+             "x_norm", "x_norm_loss"),
+            (getattr(task.args, "delta_pair_repr_norm_loss", 0.0) or 0.0,
+             "--delta-pair-repr-norm-loss", "delta_pair_repr_norm",
+             "delta_pair_repr_norm_loss"),
+        ]
 
     def dist_loss(self, dist, sample, masked):
         """Uni-Mol's masked distance loss: smooth L1 (sum) between the
@@ -40,6 +49,10 @@ class MolPretrainLoss(UnicoreLoss):
 
     def forward(self, model, sample, reduce=True):
         net_output = model(**sample["net_input"])
+        # the norm regularisers travel as a trailing dict: take it off first
+        norms = {}
+        if isinstance(net_output[-1], dict):
+            norms, net_output = net_output[-1], net_output[:-1]
         logits, coord_delta = net_output[0], net_output[1]
         if self.dist_loss_weight > 0 and len(net_output) < 3:
             raise ValueError(
@@ -72,6 +85,20 @@ class MolPretrainLoss(UnicoreLoss):
             loss = loss + self.dist_loss_weight * dist_loss
             logging_output["loss"] = loss.data
             logging_output["dist_loss"] = dist_loss.data
+        for weight, flag, key, name in self.norm_terms:
+            if weight <= 0:
+                continue
+            if key not in norms:
+                raise ValueError(
+                    f"{flag} {weight} needs a model that returns "
+                    f"'{key}' (mol_pairbias with {flag}), got "
+                    f"{sorted(norms)}"
+                )
+            # a batch mean inside a loss the trainer divides by sample_size
+            term = norms[key].float() * sample_size
+            loss = loss + weight * term
+            logging_output["loss"] = loss.data
+            logging_output[name] = term.data
         return loss, sample_size, logging_output
 
     @staticmethod
@@ -93,6 +120,11 @@ class MolPretrainLoss(UnicoreLoss):
             dist_sum = sum(log.get("dist_loss", 0) for log in logging_outputs)
             metrics.log_scalar("dist_loss", dist_sum / denom, sample_size,
                                round=3)
+        for name in ("x_norm_loss", "delta_pair_repr_norm_loss"):
+            if any(name in log for log in logging_outputs):
+                norm_sum = sum(log.get(name, 0) for log in logging_outputs)
+                metrics.log_scalar(name, norm_sum / denom, sample_size,
+                                   round=3)
 
     @staticmethod
     def logging_outputs_can_be_summed(is_train) -> bool:

@@ -33,6 +33,8 @@ from unicore_amd.modules import (
     gaussian_basis,
     gelu_dropout,
     init_bert_params,
+    pair_norm,
+    x_norm,
 )
 from unicore_amd.modules.gaussian import (
     _GaussianPairBias,
@@ -185,6 +187,17 @@ class MolPairBiasModel(BaseUnicoreModel):
             "the distance per atom-type pair, normalised gaussians and a "
             "K -> K -> heads MLP (PairGaussianEmbed)",
         )
+        parser.add_argument(
+            "--x-norm-loss", type=float, metavar="W",
+            help="weight of Uni-Mol's regulariser on the norm of the atom "
+            "representation after the last layer (0 = off)",
+        )
+        parser.add_argument(
+            "--delta-pair-repr-norm-loss", type=float, metavar="W",
+            help="weight of Uni-Mol's regulariser on the norm of the pair "
+            "track's update, final pair track - embedding bias (0 = off); "
+            "needs --coord-head equivariant",
+        )
 
     def __init__(self, args, dictionary):
         super().__init__()
@@ -233,6 +246,13 @@ class MolPairBiasModel(BaseUnicoreModel):
                     f"equivariant, got --coord-head {args.coord_head}"
                 )
             self.dist_head = PairDistHead(args.encoder_attention_heads)
+        self.with_x_norm = args.x_norm_loss > 0
+        self.with_pair_norm = args.delta_pair_repr_norm_loss > 0
+        if self.with_pair_norm and not self.equivariant:
+            raise ValueError(
+                "--delta-pair-repr-norm-loss reads the pair track: it needs "
+                f"--coord-head equivariant, got --coord-head {args.coord_head}"
+            )
         self.apply(init_bert_params)
 
     @classmethod
@@ -259,13 +279,22 @@ class MolPairBiasModel(BaseUnicoreModel):
         else:
             for layer in self.layers:
                 x = layer(x, bias, padding_mask)
+        # Uni-Mol's norm regularisers, in training and in eval
+        norms = {}
+        if self.with_x_norm:
+            norms["x_norm"] = x_norm(x, padding_mask)
+        if self.with_pair_norm:
+            norms["delta_pair_repr_norm"] = pair_norm(pair, bias, padding_mask)
         x = self.final_norm(x)
         logits = self.lm_head(x)
         if not self.equivariant:
             coord_delta = self.coord_head(x)
+        out = (logits, coord_delta.float())
         if self.with_dist:
-            return logits, coord_delta.float(), dist
-        return logits, coord_delta.float()
+            out = out + (dist,)
+        if norms:
+            out = out + (norms,)
+        return out
 
 
 @register_model_architecture("mol_pairbias", "mol_pairbias")
@@ -282,3 +311,7 @@ def base_mol_architecture(args):
     args.coord_head = getattr(args, "coord_head", "linear")
     args.dist_head = getattr(args, "dist_head", False)
     args.pair_embed = getattr(args, "pair_embed", "linear")
+    args.x_norm_loss = getattr(args, "x_norm_loss", 0.0)
+    args.delta_pair_repr_norm_loss = getattr(
+        args, "delta_pair_repr_norm_loss", 0.0
+    )

@@ -9,6 +9,7 @@ from .gaussian import gaussian_basis
 from .pair_coord import PairCoordHead, pair_coord
 from .pair_dist import PairDistHead, pair_dist
 from .pair_gauss import PairGaussianEmbed
+from .norm_loss import pair_norm, x_norm
 from .gated_mul import gated_mul
 from .triangle import triangle_multiply
 from .outer_product import outer_product_mean

@@ -455,6 +455,57 @@ def pair_gauss_supported(K, H, dtype, L) -> bool:
     )
 
 
+def pair_norm_fwd(pair, bias, pad):
+    """Pair norm regulariser: pair, bias (B,H,L,L) contiguous bf16 or fp32,
+    pad (B,L) bool or None -> (coef (B,L,L), rowerr (B,L)) fp32, both 0
+    where i or j is padded. csrc/pair_norm.hip."""
+    require_kernels()
+    return _kernels.pair_norm_forward(pair, bias, pad)
+
+
+def pair_norm_bwd(gscale, coef, pair, bias):
+    """-> (d_pair, d_bias) = (gscale[b] * coef * (pair - bias), -d_pair) in
+    the dtype of pair; gscale (B) fp32."""
+    require_kernels()
+    return _kernels.pair_norm_backward(gscale, coef, pair, bias)
+
+
+def pair_norm_supported(H, dtype, L) -> bool:
+    # mirrors the host check in csrc/bindings.cpp; pure Python so a missing
+    # extension still fails loudly in pair_norm_fwd
+    import torch
+
+    if dtype not in (torch.float32, torch.bfloat16):
+        return False
+    return (
+        int(H) >= 4 and int(H) % 4 == 0 and int(L) >= 8 and int(L) % 8 == 0
+    )
+
+
+ROW_NORM_MAX_E = 8192  # kRowNormMaxE of csrc/pair_norm.h
+
+
+def row_norm_fwd(x, pad):
+    """Row norm regulariser: x (N,E) contiguous bf16 or fp32, pad (N) bool or
+    None -> (coef (N), err (N)) fp32, 0 at padded rows."""
+    require_kernels()
+    return _kernels.row_norm_forward(x, pad)
+
+
+def row_norm_bwd(g_row, coef, x):
+    """-> dx = g_row[n] * coef[n] * x in the dtype of x; g_row (N) fp32."""
+    require_kernels()
+    return _kernels.row_norm_backward(g_row, coef, x)
+
+
+def row_norm_supported(E, dtype) -> bool:
+    import torch
+
+    if dtype not in (torch.float32, torch.bfloat16):
+        return False
+    return int(E) >= 8 and int(E) % 8 == 0 and int(E) <= ROW_NORM_MAX_E
+
+
 def softmax_dropout_bwd_bias(grad, softmax_out, dmask, p, bb, bq, od):
     """In-place softmax backward that also returns the broadcast bias grad
     (fp32, (bb*bq, k)) without re-reading the grad tensor."""
